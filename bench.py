@@ -1,7 +1,18 @@
 """Benchmark: sampled points/s (forward + backward) of the MI355X Gaussian sampler.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--function gaussian] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--function gaussian] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu] ...
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up (inputs, one binning), runs the W warmup steps and the settling steps, times
+the K steps and prints the result line: metric, value, ms_per_step and what describes the
+workload.  `--full` adds everything else the line can hold, each at its own cost: the warm
+binning medians (--pre-reps) and the PIGS binning patterns, the K steps timed before settling,
+kernels_ms and the roofline (HIP events inside the timed steps, the live-pair count), the binning's
+entry counts and the CPU baselines (--no-cpu drops those).  `--dump-outputs DIR` writes what the
+last timed step returned to its caller -- the output and the three gradients -- as DIR/<name>.npy
+(float32; a seeded row sample of each array if they exceed 64 MB together).  The inputs are seeded:
+two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs): 1M anisotropic 2-D Gaussians, C = 1.
   * N = 1: configs[2], the headline -- 1M Gaussians x 2M query points on one GPU.
@@ -16,9 +27,9 @@ Workload (BASELINE.json configs): 1M anisotropic 2-D Gaussians, C = 1.
         [dmeans | dvalues | dconics] gradients per step (the north star's formulation).
     `--weak` keeps 2M query points per GPU instead.
 One step = forward + backward through the autograd Function (+ the gradient exchange for N > 1);
-binning (preprocess) is timed separately, as the metric asks.  kernels_ms and the roofline come
-from HIP events on the render kernels' stream over every 4th timed step and the last (an event
-record opens a ~5 us gap between kernels: events on every step would add ~1.4 % to it).
+binning (preprocess) is timed separately, as the metric asks.  With --full, kernels_ms and the
+roofline come from HIP events on the render kernels' stream over every 4th timed step and the last
+(an event record opens a ~5 us gap between kernels: events on every step would add ~1.4 % to it).
 
 `python bench.py --gpus N` without a torch.distributed environment starts the N ranks itself
 (a torch.distributed.run child, before this process touches the GPU) and exits with its code;
@@ -90,6 +101,30 @@ def log(rank, *a):
         print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, torch):
+    """--dump-outputs: {name: tensor} as path/<name>.npy (float32, or float64 where the tensor is).
+    Beyond DUMP_BUDGET_BYTES in all, every array above 64 KiB keeps the same fraction of its rows
+    (dim 0), the rows drawn once with a fixed seed per row count and kept in ascending order, so
+    two runs with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: t.detach() for k, t in arrays.items() if t is not None}
+    wide = {k: (torch.float64 if t.dtype == torch.float64 else torch.float32) for k, t in arrays.items()}
+    size = {k: t.numel() * (8 if wide[k] == torch.float64 else 4) for k, t in arrays.items()}
+    whole = 128 * len(arrays) + sum(b for b in size.values() if b <= 65536)  # .npy headers, small arrays
+    total = sum(b for b in size.values() if b > 65536)
+    for name, t in arrays.items():
+        rows = t.shape[0] if t.dim() > 0 else 1
+        if total + whole > DUMP_BUDGET_BYTES and size[name] > 65536 and rows > 1:
+            keep = max(1, int(rows * ((DUMP_BUDGET_BYTES - whole) / total)))
+            pick = np.sort(np.random.default_rng(rows).choice(rows, size=keep, replace=False))
+            t = t[torch.from_numpy(pick).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(wide[name]).cpu().numpy())
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -140,7 +175,13 @@ def main():
                     help="axis ratios U[1, aniso] at the headline's areas (thin Gaussians: 25)")
     ap.add_argument("--grid", type=int, default=0,
                     help="query points on a regular g x g lattice instead of uniform (SURVEY 8d config 5: 4096)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: warm / resampled / alternating binning, "
+                         "the unsettled steps, kernels_ms and the roofline, the pair and entry counts, the "
+                         "CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's output and gradients as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-samples", type=int, default=2048,
                     help="query points of the PyTorch-eager CPU baseline sample")
     ap.add_argument("--cpu-oracle-samples", type=int, default=2048,
@@ -162,6 +203,8 @@ def main():
                     help="also time the PIGS step -- re-binning + forward + backward -- eagerly and as ONE "
                          "captured HIP graph (preprocess_gaussians_capturable, SURVEY 8f row f1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])
@@ -204,6 +247,8 @@ def bench_sample(args, world, rank, dev, torch, dist):
     N = args.N if args.N is not None else (2_000_000 if (world == 1 or args.weak) else 1_000_000)
     fn = args.function
     K = D ** FUNCS[fn]
+    full = args.full
+    pre_reps = args.pre_reps if full else 0  # a plain run bins once: the step needs one binning
     means, values, covs, conics = (t.to(dev) for t in syn.gaussians(P, D, C, seed=0, aniso=args.aniso))
     if args.grid:
         g = args.grid
@@ -244,7 +289,7 @@ def bench_sample(args, world, rank, dev, torch, dist):
     dgs.warmup()
     warmup_ms = (time.perf_counter() - t0) * 1e3
     pre_times = []
-    for _ in range(1 + args.pre_reps):
+    for _ in range(1 + pre_reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if spatial:  # only the rows this rank holds (owned or reaching its strip)
@@ -260,20 +305,20 @@ def bench_sample(args, world, rank, dev, torch, dist):
         torch.cuda.synchronize()
         pre_times.append((time.perf_counter() - t0) * 1e3)
     pre_first_ms = pre_times[0]
-    pre_ms = sorted(pre_times[1:])[len(pre_times[1:]) // 2] if args.pre_reps > 0 else pre_first_ms
+    pre_ms = sorted(pre_times[1:])[len(pre_times[1:]) // 2] if pre_reps > 0 else pre_first_ms
     R, gb, sb, rg, srg, radii = binned
     pre_extra = {}
-    if world == 1 and args.pre_reps > 0:
+    if world == 1 and pre_reps > 0:
         # the PIGS loop's other binning patterns (one GPU, reference API): fresh collocation points
         # every call (samples.min -- the grid offset -- moves each time), and two samplers whose
         # domains alternate (interior / boundary points); inputs generated before the clock starts
         med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
-        fresh = [torch.rand(N, D, device=dev) * 2.0 - 1.0 for _ in range(args.pre_reps + 1)]
+        fresh = [torch.rand(N, D, device=dev) * 2.0 - 1.0 for _ in range(pre_reps + 1)]
         # a second sampler's points: an independent draw over the same domain (another grid
         # offset, the same density and binning cost)
         other = torch.rand(N, D, device=dev, generator=torch.Generator(device=dev).manual_seed(77)) * 2.0 - 1.0
-        pats = {"preprocess_resampled_ms": [fresh[i] for i in range(args.pre_reps + 1)],
-                "preprocess_alternating_ms": [samples if i % 2 == 0 else other for i in range(2 * args.pre_reps + 2)]}
+        pats = {"preprocess_resampled_ms": [fresh[i] for i in range(pre_reps + 1)],
+                "preprocess_alternating_ms": [samples if i % 2 == 0 else other for i in range(2 * pre_reps + 2)]}
         for key, seq in pats.items():
             ts = []
             for sm in seq:
@@ -300,11 +345,11 @@ def bench_sample(args, world, rank, dev, torch, dist):
         for t in (means, values, conics):
             t.grad = None
         if multi:
-            outs = dgs.sample_gaussians_multi(multi, means, values, conics, samples, R, gb, sb, rg, srg, False)
-            torch.autograd.backward(list(outs), dLm)
+            outs = list(dgs.sample_gaussians_multi(multi, means, values, conics, samples, R, gb, sb, rg, srg, False))
+            torch.autograd.backward(outs, dLm)
         else:
-            out = fwd(means, values, conics, samples, R, gb, sb, rg, srg, False)
-            out.backward(dLv)
+            outs = [fwd(means, values, conics, samples, R, gb, sb, rg, srg, False)]
+            outs[0].backward(dLv)
         if world > 1:
             if timed:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -325,6 +370,7 @@ def bench_sample(args, world, rank, dev, torch, dist):
                 if timed:
                     p1.record()
                     push_ev.append((p0, p1))
+        return outs
 
     for _ in range(args.warmup):
         step()
@@ -342,20 +388,22 @@ def bench_sample(args, world, rank, dev, torch, dist):
             dist.barrier()
         t0 = time.perf_counter()
         for k in range(args.steps):
-            dgs._C.timing_enable(events and (k % 4 == 3 or k == args.steps - 1))
-            step(timed=True)
+            if events:
+                dgs._C.timing_enable(k % 4 == 3 or k == args.steps - 1)
+            last = step(timed=True)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
         dgs._C.timing_enable(False)
-        return el
+        return el, last
 
     # The render kernels run ~25 % slower for the first ~30 ms of sustained work (the clock ramp,
     # profiles/r04_clock_ramp.txt): K steps right after the W warmup steps are timed
     # and reported (ms_per_step_unsettled), then steps run until --settle-ms of them have passed,
     # and the K timed steps of the line follow, at the clocks a training loop runs at.
-    unsettled_ms = timed_block(False) * 1e3 / args.steps if args.settle_ms > 0 else None
+    # (--full; a plain run goes from the warmup straight to the settling steps)
+    unsettled_ms = timed_block(False)[0] * 1e3 / args.steps if full and args.settle_ms > 0 else None
     settle_steps, t_settle = 0, time.perf_counter()
 
     def settling():  # (N > 1: rank 0's clock decides, every rank steps the same number of times)
@@ -372,9 +420,14 @@ def bench_sample(args, world, rank, dev, torch, dist):
         settle_steps += 4
         torch.cuda.synchronize()
     settle_ms = (time.perf_counter() - t_settle) * 1e3
-    elapsed = timed_block(True)
+    elapsed, last = timed_block(full)  # (a plain run records no events inside its steps)
     nf, fms = dgs._C.timing_read(0)
     nb, bms = dgs._C.timing_read(1)
+    if args.dump_outputs and rank == 0:  # (N > 1: rank 0's shard and the gradients it holds)
+        named = {("out_" + f if multi else "out"): o for f, o in zip(multi or [fn], last)}
+        named.update(dmeans=means.grad, dvalues=values.grad, dconics=conics.grad)
+        dump_outputs(args.dump_outputs, named, torch)
+    del last
     rank_ms = elapsed * 1e3 / args.steps
     ar_ms = sum(a.elapsed_time(b) for a, b in ar_ev) / len(ar_ev) if ar_ev else 0.0
     if world > 1:
@@ -391,13 +444,15 @@ def bench_sample(args, world, rank, dev, torch, dist):
     value = N * world / (ms_per_step / 1e3)
 
     push_ms = sum(a.elapsed_time(b) for a, b in push_ev) / len(push_ev) if push_ev else 0.0
-    # ---- live-pair count (diagnostic kernel, outside the timed region)
-    w_cand, w_live = dgs._C.count_pairs(means.detach(), conics.detach(), samples, gb, sb, -104.0)
+    # ---- live-pair count (--full: a diagnostic kernel, outside the timed region)
+    w_cand = w_live = None
+    if full:
+        w_cand, w_live = dgs._C.count_pairs(means.detach(), conics.detach(), samples, gb, sb, -104.0)
     avg_f = fms / max(nf, 1)
     avg_b = bms / max(nb, 1)
     fname = "+".join(multi) if multi else fn
     roofline = hbm = None
-    if not multi:
+    if full and not multi:
         f_fwd, f_bwd = flops_per_live_pair(fn, C)
         b_fwd, b_bwd = algorithmic_bytes(fn, P, N, C)
         kern = {"forward_render": (avg_f, f_fwd, b_fwd), "backward_render": (avg_b, f_bwd, b_bwd)}
@@ -452,21 +507,26 @@ def bench_sample(args, world, rank, dev, torch, dist):
                    "parallelism": f"query-point shards x{world}, Gaussians replicated"
                                   + ((", spatial strips, sparse gradient exchange (RCCL all-to-all)" if spatial
                                       else ", 1 RCCL all-reduce per step") if world > 1 else "")},
-        "preprocess_ms": pre_ms,
-        # the Physics-Informed-GS loop re-bins every step (means move): its step time
-        "total_ms_per_step_incl_preprocess": ms_per_step + pre_ms,
         "preprocess_first_call_ms": pre_first_ms,
         "library_warmup_ms": warmup_ms,
-        **pre_extra,
-        "kernels_ms": {"forward_render": avg_f, "backward_render": avg_b},
-        "pairs": {"W_cand": w_cand, "W_live": w_live, "num_rendered": R},
-        "entries": dict(zip(("num_rendered", "fine_entries", "literal_path_entries", "fine_cells", "thin_entries",
-                             "sort_path_entries"),
-                            dgs._C.binning_info(gb, sb))),
-        "roofline": roofline,
-        "hbm": hbm,
-        "cpu_baseline": None,
+        "num_rendered": R,
+        "full": full,
     }
+    if full:
+        result.update({
+            "preprocess_ms": pre_ms,
+            # the Physics-Informed-GS loop re-bins every step (means move): its step time
+            "total_ms_per_step_incl_preprocess": ms_per_step + pre_ms,
+            **pre_extra,
+            "kernels_ms": {"forward_render": avg_f, "backward_render": avg_b},
+            "pairs": {"W_cand": w_cand, "W_live": w_live, "num_rendered": R},
+            "entries": dict(zip(("num_rendered", "fine_entries", "literal_path_entries", "fine_cells",
+                                 "thin_entries", "sort_path_entries"),
+                                dgs._C.binning_info(gb, sb))),
+            "roofline": roofline,
+            "hbm": hbm,
+            "cpu_baseline": None,
+        })
     if world > 1:
         F = D + C + D * (D + 1) // 2
         result["distributed"] = {"backend": dist.get_backend(), "world_size": world, "shard": args.shard,
@@ -478,7 +538,7 @@ def bench_sample(args, world, rank, dev, torch, dist):
                                  "exchange_setup_ms_once": xsetup_ms,
                                  "push_ms_rank0_in_step": push_ms,
                                  "held_rows_rank0": int(xchg.held.sum()) if spatial else P,
-                                 "w_cand_per_point_rank0": w_cand / N}
+                                 "w_cand_per_point_rank0": w_cand / N if full else None}
 
     if args.calltime and world == 1 and not multi:
         # an optimizer-like in-place step on the means (1/10 of the mean spacing), then sampling
@@ -564,7 +624,7 @@ def bench_sample(args, world, rank, dev, torch, dist):
                                         "call + backward; both copy the fixed samples' sample side from an "
                                         "earlier binning (samples_binned) instead of sorting them per step"}
         del graph
-    if rank == 0 and world == 1 and not args.no_cpu and not multi:
+    if full and rank == 0 and world == 1 and not args.no_cpu and not multi:
         cpu_baselines(result, means.detach().cpu(), values.detach().cpu(), covs.cpu(),
                       conics.detach().cpu(), samples.cpu(), dL.cpu(), fn, w_live, N, args, torch)
     if rank == 0:
@@ -663,6 +723,7 @@ def bench_volume(args, world, rank, dev, torch, dist):
             torch.cuda.synchronize()
             fwd_ms.append(ev[0].elapsed_time(ev[1]))
             bwd_ms.append(ev[1].elapsed_time(ev[2]))
+        return out
 
     # the first step also builds the transposed lists (at its backward, once per
     # preprocess_aggregate: a loop that re-runs the neighbour search every step pays it per step)
@@ -678,7 +739,7 @@ def bench_volume(args, world, rank, dev, torch, dist):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(False)
+        last = step(False)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -687,6 +748,10 @@ def bench_volume(args, world, rank, dev, torch, dist):
         e = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(out=last, dmeans=means.grad, dvalues=values.grad, dconics=conics.grad),
+                     torch)
+    del last
     step(True)
     ms = elapsed * 1e3 / args.steps
     from diff_gaussian_sampling import _C
@@ -770,6 +835,7 @@ def bench_aggregate(args, world, rank, dev, torch, dist):
             torch.cuda.synchronize()
             fwd_ms.append(ev[0].elapsed_time(ev[1]))
             bwd_ms.append(ev[1].elapsed_time(ev[2]))
+        return out
 
     # the first step also builds the transposed lists (at its backward, once per
     # preprocess_aggregate: a loop that re-runs the neighbour search every step pays it per step)
@@ -785,7 +851,7 @@ def bench_aggregate(args, world, rank, dev, torch, dist):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(False)
+        last = step(False)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -794,6 +860,12 @@ def bench_aggregate(args, world, rank, dev, torch, dist):
         e = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs and rank == 0:
+        named = {"out": last}
+        named.update({"d" + k: t.grad for k, t in zip(("features", "transform", "queries", "keys", "frequencies",
+                                                          "distance_transform"), feats_d)})
+        dump_outputs(args.dump_outputs, named, torch)
+    del last
     for _ in range(3):  # per-phase event times, outside the timed region
         step(True)
     ms_per_step = elapsed * 1e3 / args.steps
@@ -847,7 +919,7 @@ def bench_aggregate(args, world, rank, dev, torch, dist):
                 "frac": (stream_b + atomic_b) / (b_ms * 1e-3) / 1e9 / PEAK_HBM_GBS},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as orc
         from oracle import torch_eager as te
         orc.build()

@@ -5,7 +5,7 @@
 #
 #   bash tools/gpu.sh tests   TAG              pytest -m gpu (margins -> TAG/margins.json)
 #   bash tools/gpu.sh smoke   TAG              __graft_entry__.smoke()
-#   bash tools/gpu.sh bench   TAG [ARGS...]    one bench.py line (CPU baselines unless --no-cpu)
+#   bash tools/gpu.sh bench   TAG [ARGS...]    one bench.py --full line (CPU baselines unless --no-cpu)
 #   bash tools/gpu.sh prof    TAG [ARGS...]    rocprofv3 --kernel-trace --stats of bench.py --no-cpu ARGS
 #   bash tools/gpu.sh pmc     TAG [ARGS...]    FETCH_SIZE / WRITE_SIZE passes (traffic.json input)
 #   bash tools/gpu.sh sq      TAG [ARGS...]    the SQ issue / wait counters, two passes
@@ -40,7 +40,7 @@ step_smoke() {
 }
 step_bench() {  # NAME ARGS...
     local n=$1; shift
-    timeout -k 10 400 python -u bench.py "$@" > "$O/bench_$n.log" 2>&1 \
+    timeout -k 10 400 python -u bench.py --full "$@" > "$O/bench_$n.log" 2>&1 \
         || { echo "bench $n failed"; tail -5 "$O/bench_$n.log"; return 1; }
     grep '^{' "$O/bench_$n.log" | tail -1 > "$O/bench_$n.json"
     echo "bench $n: $(python -c "import json,sys; j=json.load(open('$O/bench_$n.json')); print(j['ms_per_step'], 'ms/step', j.get('kernels_ms'))")"
@@ -106,7 +106,7 @@ case $CMD in
         && step_pmc head && step_pmc thin --aniso 25 && step_pmc config2 --P 100000 --N 256000 --C 16 \
         && step_sq head \
         && { DGS_BENCH_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 \
+                 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 \
                  > "$O/bench2.log" 2>&1 && grep '^{' "$O/bench2.log" | tail -1 > "$O/bench2_rehearsal.json"; } \
         && echo ALLDONE ;;
     *) echo "unknown step $CMD"; exit 2 ;;
