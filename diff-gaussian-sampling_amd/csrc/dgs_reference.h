@@ -45,5 +45,8 @@ template <int FN, int D, int CB>
 int ref_forward(const RefCall &a);
 template <int FN, int D, int CB>
 int ref_backward(const RefCall &a);
+// dL/dsamples on the reference's pair set, added onto a.acc ([N][D], caller order; needs a.cbox).
+template <int FN, int D, int CB>
+int ref_sample_grad(const RefCall &a);
 
 }  // namespace dgs

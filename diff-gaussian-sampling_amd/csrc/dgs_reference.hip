@@ -531,6 +531,60 @@ __global__ __launch_bounds__(kBlock) void k_ref_backward(const char *__restrict_
     }
 }
 
+// The sample-position gradient (dgs_render.h: sgrad_terms) on the reference's pair set with the
+// call-time tensors, over the forward's units and candidate walk (lane = sample): each lane adds
+// its own sample's terms in list order -- no atomics -- onto dsamples (zero-filled by the call;
+// a tile's samples belong to one unit, channel blocks run in turn on the stream).
+template <int FN, int D, int CB>
+__global__ __launch_bounds__(kBlock) void k_ref_sample_grad(const char *__restrict__ gbuf, const char *__restrict__ sbuf,
+                                                            const float *__restrict__ values,
+                                                            const float *__restrict__ conics,
+                                                            const float *__restrict__ samples,
+                                                            const uint32_t *__restrict__ flag, const DLs dls,
+                                                            float *__restrict__ dsamples, int C, int cbase,
+                                                            const float4 *__restrict__ cbox) {
+    if (sload(flag) == 0u) return;  // the binned tensors were passed: k_sample_grad did it
+    constexpr int U = Traits<FN, D>::U, PFN = fn_mask(FN) == 1 ? 0 : 1;  // (the literal power's form)
+    const Bins bins = resolve(gbuf, sbuf);
+    const int T = sload(&bins.h->T);
+    const uint32_t *gst = bins.rtab + kRtGStart * (T + 1), *sst = bins.rtab + kRtSStart * (T + 1);
+    const uint32_t *fu = bins.rtab + kRtFwdUnits * (T + 1);
+    const uint32_t nunits = sload(&fu[T]);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int nch = min(CB, C - cbase);
+    const uint32_t w0 = blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint32_t unit = w0; unit < nunits; unit += gridDim.x * kWavesPerBlock) {
+        const RefUnit u = ref_unit<D>(bins, fu, sst, T, unit, samples, lane);
+        float dl[U][CB];
+        lane_dl<FN, D, CB>(dls, u.sid, u.active, C, cbase, nch, dl);
+        float ds[2] = {0.0f, 0.0f};
+        const uint32_t ge = sload(&gst[u.t + 1]);
+        RefLanes<D, CB> cur, nxt;
+        uint32_t e0 = sload(&gst[u.t]);
+        ref_lane_load<D, CB>(bins, cbox, e0 + lane, ge, nxt);
+        for (; e0 < ge; e0 += kWave) {
+            cur.g = nxt.g;
+            cur.b = nxt.b;
+            if (e0 + kWave < ge) ref_lane_load<D, CB>(bins, cbox, e0 + kWave + lane, ge, nxt);
+            uint64_t cand = ref_group_lanes<D, CB>(conics, values, C, cbase, nch, u, e0 + lane < ge, cur);
+            while (cand) {
+                const int b = __builtin_ctzll(cand);
+                cand &= cand - 1;
+                float m[2], c[3], v[CB];
+                ref_take<D, CB>(cur, b, m, c, v);
+                float X[2];
+                ref_displacement<D>(m, u.s, X);
+                const float p = ref_power<PFN, D>(X, c);
+                if (!(p > 0.0f)) sgrad_terms<FN, D, CB>(X, c, expf(p), v, dl, ds);  // forward.cu:228
+            }
+        }
+        if (u.active) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) dsamples[u.sid * D + d] += ds[d];
+        }
+    }
+}
+
 // Persistent grids: the work is known only on the device; when the flag is clear every block
 // exits after one scalar load.
 static unsigned ref_blocks(int64_t units) {  // (up to 8 waves per SIMD: the walk is latency-bound)
@@ -556,9 +610,20 @@ int ref_backward(const RefCall &a) {
     return DGS_OK;
 }
 
+template <int FN, int D, int CB>
+int ref_sample_grad(const RefCall &a) {
+    if (!a.cbox) return fail(DGS_ERR_ARG, "ref_sample_grad: the call-time cuts' region is required");
+    const int64_t cap = a.N / kRefUnit + (a.N + 1);  // (the forward's units)
+    k_ref_sample_grad<FN, D, CB><<<ref_blocks(cap), kBlock, 0, a.s>>>(a.gb, a.sb, a.values, a.conics, a.samples,
+                                                                      a.flag, a.dls, a.acc, a.C, a.cbase, a.cbox);
+    DGS_LAUNCH_CHECK(a.s, a.debug);
+    return DGS_OK;
+}
+
 #define DGS_REF_INST(FN, D, CB)                            \
     template int ref_forward<FN, D, CB>(const RefCall &);  \
-    template int ref_backward<FN, D, CB>(const RefCall &);
+    template int ref_backward<FN, D, CB>(const RefCall &); \
+    template int ref_sample_grad<FN, D, CB>(const RefCall &);
 #define DGS_REF_INST_CB(FN, D) \
     DGS_REF_INST(FN, D, 1) DGS_REF_INST(FN, D, 2) DGS_REF_INST(FN, D, 4) DGS_REF_INST(FN, D, 8) DGS_REF_INST(FN, D, 16)
 DGS_REF_INST_CB(0, 1) DGS_REF_INST_CB(0, 2)

@@ -587,6 +587,124 @@ __device__ __forceinline__ void bwd_mom_finish(const float *c, float v, const fl
     gc[2] = v * fmaf(-0.5f, s[7], s[10]);
 }
 
+// ---------------------------------------------------------------------------------------
+// Gradient with respect to the sample position (dgs_sample_backward_samples).
+//
+// With the notation of the moment form above (phi = sum_u h_u t_u(a, c), g = d phi / d a,
+// h_u = sum_ch v_ch dL_u,ch) the pair's loss is G phi, a function of X = wrap(m - s) alone, so
+//   dL/ds = -dL/dm = G (phi a - A g)
+// (the wrap has derivative 1 almost everywhere).  g follows from fwd_terms' t_u:
+//   gaussian   t = 1                          g = 0
+//   derivative t = (a1, a2)                   g = (h0, h1)
+//   laplacian  t = (a1 a1 - c0, a1 a2 - c1, a2 a2 - c2)
+//                                             g = (2 h0 a1 + h1 a2, h1 a1 + 2 h2 a2)
+//   third      t = (a1 (3 c0 - a1 a1), 2 c1 a1 + a2 (c0 - a1 a1),
+//                   2 c1 a2 + a1 (c2 - a2 a2), a2 (3 c2 - a2 a2)); with p = c0 - a1 a1,
+//              r = c1 - a1 a2, s = c2 - a2 a2:
+//                                             g = (3 h0 p + 2 h1 r + h2 s, h1 p + 2 h2 r + 3 h3 s)
+// -- the fourth-order terms of the third function enter through A g.  D = 1: a = c X and
+// t = 1, a, a a - c, 3 c a - a a a; g = 0, h, 2 h a, 3 h (c - a a).
+// dl: the sample's dL summed over symmetric components, [U of the mask][CB] (lane_dl).
+// ---------------------------------------------------------------------------------------
+// D = 2, written once over V (float: one pair per lane; f2: two pairs, packed fp32 ops).
+// h: the mask's H_u (dL summed over symmetric components and channels, values folded in or into G).
+template <int M, typename V>
+__device__ __forceinline__ void sgrad2(const V *X, const float *c, V G, const V *h, V *ds) {
+    const V a1 = vfma(bc<V>(c[1]), X[1], c[0] * X[0]);
+    const V a2 = vfma(bc<V>(c[1]), X[0], c[2] * X[1]);
+    V phi = bc<V>(0.0f), g0 = bc<V>(0.0f), g1 = bc<V>(0.0f);
+    if constexpr ((M & 1) != 0) phi = h[mask_uoff(M, 2, 0)];
+    if constexpr ((M & 2) != 0) {
+        const V *q = h + mask_uoff(M, 2, 1);
+        phi = vfma(q[0], a1, vfma(q[1], a2, phi));
+        g0 += q[0];
+        g1 += q[1];
+    }
+    if constexpr ((M & 4) != 0) {
+        const V *q = h + mask_uoff(M, 2, 2);
+        const V t0 = vfma(a1, a1, bc<V>(-c[0])), t1 = vfma(a1, a2, bc<V>(-c[1])), t2 = vfma(a2, a2, bc<V>(-c[2]));
+        phi = vfma(q[2], t2, vfma(q[1], t1, vfma(q[0], t0, phi)));
+        g0 = vfma(2.0f * q[0], a1, vfma(q[1], a2, g0));
+        g1 = vfma(2.0f * q[2], a2, vfma(q[1], a1, g1));
+    }
+    if constexpr ((M & 8) != 0) {
+        const V *q = h + mask_uoff(M, 2, 3);
+        const V p = vfma(-a1, a1, bc<V>(c[0])), r = vfma(-a1, a2, bc<V>(c[1])), s = vfma(-a2, a2, bc<V>(c[2]));
+        const V t0 = a1 * (p + bc<V>(2.0f * c[0]));            // a1 (3 c0 - a1 a1)
+        const V t1 = vfma(bc<V>(2.0f * c[1]), a1, a2 * p);
+        const V t2 = vfma(bc<V>(2.0f * c[1]), a2, a1 * s);
+        const V t3 = a2 * (s + bc<V>(2.0f * c[2]));
+        phi = vfma(q[3], t3, vfma(q[2], t2, vfma(q[1], t1, vfma(q[0], t0, phi))));
+        g0 = vfma(3.0f * q[0], p, vfma(2.0f * q[1], r, vfma(q[2], s, g0)));
+        g1 = vfma(q[1], p, vfma(2.0f * q[2], r, vfma(3.0f * q[3], s, g1)));
+    }
+    ds[0] = vfma(G, vfma(phi, a1, -vfma(bc<V>(c[0]), g0, c[1] * g1)), ds[0]);
+    ds[1] = vfma(G, vfma(phi, a2, -vfma(bc<V>(c[1]), g0, c[2] * g1)), ds[1]);
+}
+
+template <int FN, int D, int CB>
+__device__ __forceinline__ void sgrad_terms(const float *X, const float *c, float G, const float *v,
+                                            const float (&dl)[Traits<FN, D>::U][CB], float *ds) {
+    constexpr int M = fn_mask(FN), U = Traits<FN, D>::U;
+    float h[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float s = 0.0f;
+#pragma unroll
+        for (int ch = 0; ch < CB; ++ch) s = fmaf(v[ch], dl[u][ch], s);
+        h[u] = s;
+    }
+    if constexpr (D == 1) {
+        float phi = 0.0f;
+        const float a = c[0] * X[0];
+        float g = 0.0f;
+        if constexpr ((M & 1) != 0) phi = h[mask_uoff(M, D, 0)];
+        if constexpr ((M & 2) != 0) {
+            const float h1 = h[mask_uoff(M, D, 1)];
+            phi = fmaf(h1, a, phi);
+            g += h1;
+        }
+        if constexpr ((M & 4) != 0) {
+            const float h2 = h[mask_uoff(M, D, 2)];
+            phi = fmaf(h2, fmaf(a, a, -c[0]), phi);
+            g = fmaf(2.0f * h2, a, g);
+        }
+        if constexpr ((M & 8) != 0) {
+            const float h3 = h[mask_uoff(M, D, 3)];
+            const float p = fmaf(-a, a, c[0]);
+            phi = fmaf(h3, a * fmaf(2.0f, c[0], p), phi);  // 3 c a - a^3 = a (2 c + p)
+            g = fmaf(3.0f * h3, p, g);
+        }
+        ds[0] = fmaf(G, fmaf(phi, a, -c[0] * g), ds[0]);
+    } else {
+        sgrad2<M, float>(X, c, G, h, ds);
+    }
+}
+
+// A lane's (sample's) dL of every function of the mask, summed over symmetric components:
+// dl[mask_uoff(f) + u][ch].  Inactive lanes get zeros.
+template <int FN, int D, int CB>
+__device__ __forceinline__ void lane_dl(const DLs &dls, int64_t sid, bool active, int C, int cbase, int nch,
+                                        float (&dl)[Traits<FN, D>::U][CB]) {
+    constexpr int M = fn_mask(FN), U = Traits<FN, D>::U;
+#pragma unroll
+    for (int a = 0; a < U; ++a)
+#pragma unroll
+        for (int ch = 0; ch < CB; ++ch) dl[a][ch] = 0.0f;
+    if (!active) return;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        if (!(M & (1 << f))) continue;
+        const int K = fn_k(f, D), o = mask_uoff(M, D, f);
+        const float *d = dls.p[f] + sid * K * C + cbase;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int ch = 0; ch < CB; ++ch)
+                if (ch < nch) dl[o + unique_fk(f, D, k)][ch] += d[k * C + ch];
+    }
+}
+
 // Epilogue of the gaussian moment form: convert moments to gradients.
 template <int FN, int D>
 __device__ __forceinline__ void bwd_finish(const float *c, float *gm, float *gc) {

@@ -787,6 +787,275 @@ __global__ __launch_bounds__(kBlock) void k_forward(const char *__restrict__ gbu
     }
 }
 
+// ------------------------------------------------------------- sample-position gradient
+// dL/dsamples (dgs_sample_backward_samples): a per-sample gather over the forward's pair set,
+// in the lane-per-sample form of k_forward -- lane = sample of the unit with its own dL in
+// registers, the cell's Gaussian rows walked wave-uniformly through the scalar cache (rows of
+// k_pack_gauss<1, D, CB>: the raw conic is in the row for every function).  No atomics: one
+// lane owns a sample, the list order fixes the order of the additions.  A lane reads no other
+// sample's dL, so a non-finite dL stays in its own sample's gradient.  Flagged entries take
+// the forward's general path (constant or exact wrap, the reference-literal power).
+// Channel blocks after the first add onto the gradient (the loss is a sum over channels).
+// TAIL = true: only the unsafe-conic entries (all in the flagged tail [gm, ge) of a list), added
+// onto the sub-cell kernel's gradient (k_sample_grad_s), which covered every other entry.
+template <int FN, int D, int CB, bool TAIL>
+__global__ __launch_bounds__(kBlock) void k_sample_grad(const char *__restrict__ gbuf,
+                                                        const char *__restrict__ sbuf,
+                                                        const float *__restrict__ grows,
+                                                        const float *__restrict__ samples, const DLs dls,
+                                                        float *__restrict__ dsamples, int C, int cbase,
+                                                        const uint32_t *__restrict__ dirty) {
+    if (sload(dirty)) return;  // call-time tensors differ from the binned ones: dgs_reference.hip
+    constexpr int U = Traits<FN, D>::U;
+    constexpr int RS = grow_stride<1, D, CB>(), B = Traits<1, D>::GBASE, NB = fwd_batch<RS>();
+    const Bins bins = resolve(gbuf, sbuf);
+    const int nunits = sload(&bins.counts[kNumFwdUnits]);
+    const int stride = gridDim.x * kWavesPerBlock;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int nch = min(CB, C - cbase);
+    const char *gbase = reinterpret_cast<const char *>(grows);
+    if (TAIL && sload(&bins.counts[kNumUnsafe]) == 0) return;  // no unsafe entry anywhere
+    for (int unit = wave_unit_index(nunits); unit < nunits; unit += stride) {
+        const FwdUnit fu = fwd_unit_at(bins, unit);
+        if (TAIL && sload(&bins.cell_gmid[fu.cell]) == sload(&bins.cell_gend[fu.cell])) continue;
+        const int j = fu.sb + lane;
+        const bool active = j >= fu.lo && j < fu.hi;
+        const int64_t sid = bins.sorted_sid[active ? j : fu.lo];
+        const float s0 = samples[sid * D], s1 = D == 2 ? samples[sid * D + 1] : 0.0f;
+        float dl[U][CB];
+        lane_dl<FN, D, CB>(dls, sid, active, C, cbase, nch, dl);
+        const int gb = sload(&bins.cell_gbeg[fu.cell]), ge = sload(&bins.cell_gend[fu.cell]);
+        const int gm = sload(&bins.cell_gmid[fu.cell]);
+        const int fe = TAIL ? gm : min(ge, gm);
+        float ds[2] = {0.0f, 0.0f};
+        int e0 = TAIL ? gm : gb;
+        for (; e0 + NB <= fe; e0 += NB) {  // flag-free entries: NB rows in flight, then the math
+            const U32s<NB> E = sload_u<NB>(bins.entries + e0);
+            F32s<RS> rows[NB];
+#pragma unroll
+            for (int q = 0; q < NB; ++q)
+                rows[q] = sload_f<RS>(reinterpret_cast<const float *>(gbase + E.v[q] * (uint32_t)(RS * 4)));
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+                const float(&r)[RS] = rows[q].v;
+                float c[3];
+                row_conic<1, D, RS>(r, c);
+                const float X[2] = {r[0] - s0, D == 2 ? r[1] - s1 : 0.0f};
+                sgrad_terms<FN, D, CB>(X, c, fast_prob<D, float>(X, &r[D]), &r[B], dl, ds);
+            }
+        }
+        for (; e0 < ge; ++e0) {  // the rest one by one: fast tail, then the flagged entries
+            const uint32_t e = sload(&bins.entries[e0]);
+            if (TAIL && !(e & kUnsafe)) continue;
+            const uint32_t id = e & kIdMask;
+            const F32s<RS> row = sload_f<RS>(reinterpret_cast<const float *>(gbase + id * (uint32_t)(RS * 4)));
+            const float(&r)[RS] = row.v;
+            float c[3];
+            row_conic<1, D, RS>(r, c);
+            float X[2] = {r[0] - s0, D == 2 ? r[1] - s1 : 0.0f};
+            float G;
+            if (!(e & kSlow)) {
+                G = fast_prob<D, float>(X, &r[D]);
+            } else {  // (FN of the literal power: gaussian and the others differ in their rounding)
+                G = general_prob<(fn_mask(FN) == 1 ? 0 : 1), D>(X, c, &r[D], (e & kGeneral) != 0, (e & kUnsafe) != 0);
+            }
+            sgrad_terms<FN, D, CB>(X, c, G, &r[B], dl, ds);
+        }
+        if (active) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                float *p = dsamples + sid * D + d;
+                *p = cbase == 0 && !TAIL ? ds[d] : *p + ds[d];
+            }
+        }
+    }
+}
+
+// The hot path (D = 2, C = 1, every mask): the transposed gather of k_forward_s over the sub
+// units and sub lists.  Lane = Gaussian (rows of k_pack_gauss<1, 2, 1> by vector gather, groups
+// software-pipelined as in fwd_s_groups); the pass's sample pairs are wave-uniform: positions from
+// the binning's sorted pair rows, hoisted into SGPRs for the list walk, and the samples' H_u
+// (dL summed over symmetric components) from pair rows packed per call (k_pack_sgrad_h), read
+// through the scalar cache per block of 4 pairs.  Packed fp32 pair math (sgrad2<M, f2>, v folded
+// into G); each lane keeps 2 partial sums per sample, so one reduce_scatter64 covers the 32
+// samples of a pass and leaves dL/ds_d of sample ps + (l >> 1) in lane l.  Every accumulator
+// belongs to one sample and the reduce-scatter only adds values of equal index, so a sample's
+// dL -- also a non-finite one, also that of a foreign sample read past the unit's end, which
+// is never stored -- reaches no other sample's gradient.
+template <int FN>
+__host__ __device__ constexpr int sg_hstride() { return (2 * Traits<FN, 2>::U + 3) / 4 * 4; }  // floats per pair row
+static int sg_hstride_rt(int FN) { return (2 * mask_sum(fn_mask(FN), 2, 1) + 3) / 4 * 4; }
+constexpr int kSgPad = 8;  // pair rows after the last (a pass reads whole blocks of 4 pairs)
+
+template <int FN>
+__global__ void k_pack_sgrad_h(int N, const char *__restrict__ gbuf, const char *__restrict__ sbuf, const DLs dls,
+                               float *__restrict__ hrows) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ((int64_t)N + 1) / 2 * 2) return;
+    constexpr int M = fn_mask(FN), U = Traits<FN, 2>::U, PH = sg_hstride<FN>();
+    float h[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) h[u] = 0.0f;
+    if (j < N) {  // j == N (odd N): the zero second half of the last pair
+        const Header *hd = reinterpret_cast<const Header *>(gbuf);
+        const int64_t sid = reinterpret_cast<const int32_t *>(sbuf + hd->o_sorted)[j];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            if (!(M & (1 << f))) continue;
+            const int K = fn_k(f, 2), o = mask_uoff(M, 2, f);
+            const float *d = dls.p[f] + sid * K;
+#pragma unroll
+            for (int k = 0; k < K; ++k) h[o + unique_fk(f, 2, k)] += d[k];
+        }
+    }
+    float *row = hrows + (j >> 1) * PH + (j & 1);
+#pragma unroll
+    for (int u = 0; u < U; ++u) row[2 * u] = h[u];
+}
+
+template <int FN, int NPH, int HB, bool WRAP>
+__device__ __forceinline__ void sg_s_pairs(const F32s<16> (&hr)[HB], const float *__restrict__ prow,
+                                           const float *__restrict__ hrow, int np, const float *m, const float *sh,
+                                           const float *c, const float *kk, float v, f2 (&acc)[NPH][2]) {
+    constexpr int PPL = 4, NB = (NPH + PPL - 1) / PPL, PH = sg_hstride<FN>(), U = Traits<FN, 2>::U;
+    constexpr bool BLOCK = PPL * PH <= 32;  // the block's H rows in one or two loads (else per pair)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (b * PPL >= np) break;  // wave-uniform: the rest of the pass is padding
+        F32s<16> t;
+        if (b < HB) t = hr[b < HB ? b : 0];
+        else t = sload_f<16>(prow + (int64_t)b * 16);
+        F32s<BLOCK ? PPL * PH : 4> hb;
+        if constexpr (BLOCK) hb = sload_f<PPL * PH>(hrow + (int64_t)b * PPL * PH);
+#pragma unroll
+        for (int j = 0; j < PPL; ++j) {
+            if (b * PPL + j >= NPH) continue;
+            const float *pr = &t.v[j * 4];
+            f2 X[2] = {m[0] - f2{pr[0], pr[1]}, m[1] - f2{pr[2], pr[3]}};
+            if constexpr (WRAP) {
+                X[0] = X[0] - sh[0];
+                X[1] = X[1] - sh[1];
+            }
+            f2 h[U];
+            if constexpr (BLOCK) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) h[u] = f2{hb.v[j * PH + 2 * u], hb.v[j * PH + 2 * u + 1]};
+            } else {
+                const F32s<PH> hp = sload_f<PH>(hrow + (int64_t)(b * PPL + j) * PH);
+#pragma unroll
+                for (int u = 0; u < U; ++u) h[u] = f2{hp.v[2 * u], hp.v[2 * u + 1]};
+            }
+            sgrad2<fn_mask(FN), f2>(X, c, fast_prob<2, f2>(X, kk) * v, h, acc[b * PPL + j]);
+        }
+    }
+}
+
+// FLAGGED: every lane but the kUnsafe ones (the tail pass), with the lane's constant wrap shift.
+template <int FN, int NPH, int HB, bool FLAGGED>
+__device__ __forceinline__ void sg_s_group(const F32s<16> (&hr)[HB], const float *__restrict__ prow,
+                                           const float *__restrict__ hrow, float (&r)[grow_stride<1, 2, 1>()],
+                                           uint32_t ent, bool active, int np, const float *ctr, f2 (&acc)[NPH][2]) {
+    constexpr int RS = grow_stride<1, 2, 1>(), B = Traits<1, 2>::GBASE;
+    bool on = active;
+    if constexpr (FLAGGED) {  // (zero row: G = 1, v = 0, a = 0 -- adds exactly 0)
+        on = active && !(ent & kUnsafe);
+        if (!on) {
+#pragma unroll
+            for (int k = 0; k < RS; ++k) r[k] = 0.0f;
+        }
+    } else {  // (a padding lane holds a copy of a well-conditioned row: zero value suffices)
+        if (!active) r[B] = 0.0f;
+    }
+    const float c[3] = {r[5], r[6], r[7]};
+    const float m[2] = {r[0], r[1]};
+    float sh[2] = {0.0f, 0.0f};
+    if constexpr (FLAGGED) {
+        if (on && (ent & kGeneral)) {
+#pragma unroll
+            for (int d = 0; d < 2; ++d) sh[d] = wrap_shift_f(m[d] - ctr[d]);
+        }
+    }
+    sg_s_pairs<FN, NPH, HB, FLAGGED>(hr, prow, hrow, np, m, sh, c, &r[2], r[B], acc);
+}
+
+template <int FN, int NPH, int HB, bool FLAGGED>
+__device__ __forceinline__ void sg_s_groups(const uint32_t *__restrict__ ents, const float *__restrict__ grows,
+                                            const F32s<16> (&hr)[HB], const float *__restrict__ prow,
+                                            const float *__restrict__ hrow, int eb, int ee, int np, int lane,
+                                            const float *ctr, f2 (&acc)[NPH][2]) {
+    constexpr int RS = grow_stride<1, 2, 1>();
+    if (eb >= ee) return;
+    const int last = ee - 1;
+    uint32_t e_cur = ents[min(eb + lane, last)];
+    uint32_t e_nxt = ents[min(eb + kWave + lane, last)];
+    float r_cur[RS];
+    load_grow<RS>(grows, e_cur, r_cur);
+    for (int g0 = eb; g0 < ee; g0 += kWave) {
+        float r_nxt[RS];
+        load_grow<RS>(grows, e_nxt, r_nxt);  // (a clamped, valid row past the list's end)
+        const uint32_t e_nn = ents[min(g0 + 2 * kWave + lane, last)];
+        bool work = true;  // flagged groups with no lane for this pass (all kUnsafe) are skipped
+        if constexpr (FLAGGED) {
+            const bool act = g0 + lane < ee;
+            work = __builtin_amdgcn_readfirstlane((uint32_t)(__ballot(act && (e_cur & kUnsafe) == 0) != 0ull)) != 0u;
+        }
+        if (work) sg_s_group<FN, NPH, HB, FLAGGED>(hr, prow, hrow, r_cur, e_cur, g0 + lane < ee, np, ctr, acc);
+#pragma unroll
+        for (int k = 0; k < RS; ++k) r_cur[k] = r_nxt[k];
+        e_cur = e_nxt;
+        e_nxt = e_nn;
+    }
+}
+
+template <int FN>
+__global__ __launch_bounds__(kBlock) void k_sample_grad_s(const char *__restrict__ gbuf, const char *__restrict__ sbuf,
+                                                          const float *__restrict__ grows,
+                                                          const float *__restrict__ hrows,
+                                                          float *__restrict__ dsamples,
+                                                          const uint32_t *__restrict__ dirty) {
+    if (sload(dirty)) return;  // call-time tensors differ from the binned ones: dgs_reference.hip
+    constexpr int NPH = 16, NS = 2 * NPH, PPL = 4, NB = NPH / PPL, HB = NB < DGS_FWD_HB ? NB : DGS_FWD_HB;
+    constexpr int PH = sg_hstride<FN>();
+    const Bins bins = resolve(gbuf, sbuf);
+    const float *__restrict__ fsrows = bins.fsrows;
+    const int nunits = sload(&bins.counts[kNumFwdSubUnits]);
+    const int stride = gridDim.x * kWavesPerBlock;
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int unit = wave_unit_index(nunits); unit < nunits; unit += stride) {
+        const uint2 u = sload(&bins.fsub_units[unit]);
+        const int sc = (int)u.x, cell = sc / kSubPerCell, sb = (int)u.y;
+        const int lo = max(sb, sload(&bins.sub_sbeg[sc]));
+        const int hi = min(sb + 2 * kSubPairs, sload(&bins.sub_send[sc]));
+        const int gb = sload(&bins.sub_lbeg[sc]), gm = sload(&bins.sub_lmid[sc]), gt = sload(&bins.sub_lthin[sc]);
+        float ctr[2];
+        cell_center<2>(bins, cell, ctr);
+        for (int ps = sb; ps < hi; ps += NS) {
+            const int np = __builtin_amdgcn_readfirstlane(min(NPH, (hi - ps + 1) >> 1));
+            const float *prow = fsrows + (int64_t)(ps >> 1) * 4;
+            const float *hrow = hrows + (int64_t)(ps >> 1) * PH;
+            F32s<16> hr[HB];  // the pass's first pair rows, in SGPRs for the whole list walk
+#pragma unroll
+            for (int b = 0; b < HB; ++b) hr[b] = sload_f<16>(prow + (int64_t)b * 16);
+            f2 acc[NPH][2];
+#pragma unroll
+            for (int q = 0; q < NPH; ++q) acc[q][0] = acc[q][1] = bc<f2>(0.0f);
+            sg_s_groups<FN, NPH, HB, false>(bins.sub_ent, grows, hr, prow, hrow, gb, gm, np, lane, ctr, acc);
+            if (gm < gt) sg_s_groups<FN, NPH, HB, true>(bins.sub_ent, grows, hr, prow, hrow, gm, gt, np, lane, ctr, acc);
+            float x[64];  // value index = 2 * sample + d
+#pragma unroll
+            for (int q = 0; q < NPH; ++q)
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                    x[4 * q + d] = acc[q][d].x;
+                    x[4 * q + 2 + d] = acc[q][d].y;
+                }
+            const float sum = reduce_scatter64(x, lane);
+            const int j = ps + (lane >> 1);
+            if (j >= lo && j < hi) dsamples[(int64_t)bins.sorted_sid[j] * 2 + (lane & 1)] = sum;
+        }
+    }
+}
+
 // (c) Matrix-core form (wide accumulators, CB >= 8).  For a unit's samples the forward is
 // out[s][u][ch] = sum_g A_u[s][g] v[g][ch] with A_u = G t_u (the exponent and the terms of
 // forward.cu:225-332): a [samples x Gaussians] by [Gaussians x channels] product.  A_u comes
@@ -1973,50 +2242,121 @@ static int run_backward(const Call &a) {
     return DGS_OK;
 }
 
+// The sample-position gradient's workspace: the Gaussian rows (k_pack_gauss<1, D, CB>: with the
+// raw conic, for every function) and the call's input-check word.
+// D = 2, C = 1 (the sub-cell kernel): plus the samples' H pair rows (k_pack_sgrad_h).
+static WsLayout sgrad_layout(int FN, int P, int D, int N, int C) {
+    WsLayout w;
+    w.grows = a256((size_t)P * grow_stride_rt(1, D, channel_block(C)) * 4 + 64);
+    w.srows = D == 2 && C == 1 ? a256((((size_t)N + 1) / 2 + kSgPad) * sg_hstride_rt(FN) * 4) : 0;
+    w.acc = 0;
+    w.flag = w.grows + w.srows;
+    w.total = w.flag + 256;
+    return w;
+}
+
+// dL/dsamples of the call (a.dm: [N][D], zero-filled by the caller on the stream).
+template <int FN, int D, int CB>
+static int run_sample_grad(const Call &a) {
+    const WsLayout w = sgrad_layout(FN, a.P, D, a.N, a.C);
+    float *grows = reinterpret_cast<float *>(a.ws);
+    float *hrows = reinterpret_cast<float *>(a.ws + w.grows);
+    const bool binned = (a.opts & DGS_SAMPLE_INPUTS_BINNED) != 0;
+    uint32_t *const flag = dirty_word(a, reinterpret_cast<uint32_t *>(a.ws + w.flag));
+    const unsigned blocks = unit_blocks(a.gb, a.gbytes, a.sb, a.sbytes, false);
+    UnitHint hint;  // without a hint (foreign buffers) the tail pass runs unconditionally
+    hint.nunsafe = -1;
+    const bool hinted = hint_get(a.gb, a.gbytes, a.sb, a.sbytes, &hint);
+    const bool has_unsafe = !hinted || hint.nunsafe != 0;
+    if (!binned)
+        if (int rc = ensure_ref_lists(a.gb, a.gbytes, a.sb, a.sbytes, a.s, a.debug)) return rc;
+    for (int cbase = 0; cbase < a.C; cbase += CB) {
+        k_pack_gauss<1, D, CB><<<grid_for(a.P), kBlock, 0, a.s>>>(a.P, a.gb, a.values, a.C, cbase, grows,
+                                                                  cbase == 0 && !binned ? flag : nullptr);
+        DGS_LAUNCH_CHECK(a.s, a.debug);
+        if (cbase == 0 && !binned) {
+            const int rc = verify_inputs(a.gb, a.sb, a.P, D, a.N, a.means, a.conics, a.samples, flag, a.s, a.debug);
+            if (rc) return rc;
+        }
+        if constexpr (D == 2 && CB == 1) {  // (C = 1) the sub-cell kernel, then the unsafe entries
+            k_pack_sgrad_h<FN><<<grid_for((int64_t)a.N + 1), kBlock, 0, a.s>>>(a.N, a.gb, a.sb, a.dls, hrows);
+            DGS_LAUNCH_CHECK(a.s, a.debug);
+            const unsigned sub_blocks = unit_blocks(a.gb, a.gbytes, a.sb, a.sbytes, false, kWavesPerBlock, true);
+            k_sample_grad_s<FN><<<sub_blocks, kBlock, 0, a.s>>>(a.gb, a.sb, grows, hrows, a.dm, flag);
+            DGS_LAUNCH_CHECK(a.s, a.debug);
+            if (has_unsafe) {
+                const unsigned tb = hint.nunsafe > 0 ? blocks : std::min(blocks, 1024u);
+                k_sample_grad<FN, D, CB, true><<<tb, kBlock, 0, a.s>>>(a.gb, a.sb, grows, a.samples, a.dls, a.dm, a.C,
+                                                                       cbase, flag);
+                DGS_LAUNCH_CHECK(a.s, a.debug);
+            }
+        } else {
+            k_sample_grad<FN, D, CB, false><<<blocks, kBlock, 0, a.s>>>(a.gb, a.sb, grows, a.samples, a.dls, a.dm,
+                                                                        a.C, cbase, flag);
+            DGS_LAUNCH_CHECK(a.s, a.debug);
+        }
+        if (!binned) {  // the call-time path (after k_sample_grad, the reader of the Gaussian rows)
+            const RefCall rc_ = ref_call(a, a.dm, flag, cbase, grows);
+            int rc = ref_boxes<D>(rc_);
+            if (!rc) rc = ref_sample_grad<FN, D, CB>(rc_);
+            if (rc) return rc;
+        }
+    }
+    return DGS_OK;
+}
+
+enum { kFwd = 0, kBwd = 1, kSampleGrad = 2 };
+
+template <int FN, int D, int CB>
+static int run_kind(const Call &a, int kind) {
+    return kind == kSampleGrad ? run_sample_grad<FN, D, CB>(a) : kind == kBwd ? run_backward<FN, D, CB>(a)
+                                                                               : run_forward<FN, D, CB>(a);
+}
+
 template <int FN, int D>
-static int dispatch_cb(const Call &a, bool bwd) {
+static int dispatch_cb(const Call &a, int kind) {
     switch (channel_block(a.C)) {
-    case 1: return bwd ? run_backward<FN, D, 1>(a) : run_forward<FN, D, 1>(a);
-    case 2: return bwd ? run_backward<FN, D, 2>(a) : run_forward<FN, D, 2>(a);
-    case 4: return bwd ? run_backward<FN, D, 4>(a) : run_forward<FN, D, 4>(a);
-    case 8: return bwd ? run_backward<FN, D, 8>(a) : run_forward<FN, D, 8>(a);
-    default: return bwd ? run_backward<FN, D, 16>(a) : run_forward<FN, D, 16>(a);
+    case 1: return run_kind<FN, D, 1>(a, kind);
+    case 2: return run_kind<FN, D, 2>(a, kind);
+    case 4: return run_kind<FN, D, 4>(a, kind);
+    case 8: return run_kind<FN, D, 8>(a, kind);
+    default: return run_kind<FN, D, 16>(a, kind);
     }
 }
 
 template <int FN>
-static int dispatch_d(const Call &a, bool bwd) {
-    return a.D == 1 ? dispatch_cb<FN, 1>(a, bwd) : dispatch_cb<FN, 2>(a, bwd);
+static int dispatch_d(const Call &a, int kind) {
+    return a.D == 1 ? dispatch_cb<FN, 1>(a, kind) : dispatch_cb<FN, 2>(a, kind);
 }
 
 // Fused masks (two or more functions; D = 2, C = 1): one instantiation per mask.
 template <int M>
-static int run_multi(const Call &a, bool bwd) {
-    return bwd ? run_backward<kMulti + M, 2, 1>(a) : run_forward<kMulti + M, 2, 1>(a);
+static int run_multi(const Call &a, int kind) {
+    return run_kind<kMulti + M, 2, 1>(a, kind);
 }
-static int dispatch_multi(const Call &a, bool bwd) {
+static int dispatch_multi(const Call &a, int kind) {
     switch (fn_mask(a.FN)) {
-    case 3: return run_multi<3>(a, bwd);
-    case 5: return run_multi<5>(a, bwd);
-    case 6: return run_multi<6>(a, bwd);
-    case 7: return run_multi<7>(a, bwd);
-    case 9: return run_multi<9>(a, bwd);
-    case 10: return run_multi<10>(a, bwd);
-    case 11: return run_multi<11>(a, bwd);
-    case 12: return run_multi<12>(a, bwd);
-    case 13: return run_multi<13>(a, bwd);
-    case 14: return run_multi<14>(a, bwd);
-    default: return run_multi<15>(a, bwd);
+    case 3: return run_multi<3>(a, kind);
+    case 5: return run_multi<5>(a, kind);
+    case 6: return run_multi<6>(a, kind);
+    case 7: return run_multi<7>(a, kind);
+    case 9: return run_multi<9>(a, kind);
+    case 10: return run_multi<10>(a, kind);
+    case 11: return run_multi<11>(a, kind);
+    case 12: return run_multi<12>(a, kind);
+    case 13: return run_multi<13>(a, kind);
+    case 14: return run_multi<14>(a, kind);
+    default: return run_multi<15>(a, kind);
     }
 }
 
-static int dispatch(const Call &a, bool bwd) {
-    if (is_multi(a.FN)) return dispatch_multi(a, bwd);
+static int dispatch(const Call &a, int kind) {
+    if (is_multi(a.FN)) return dispatch_multi(a, kind);
     switch (a.FN) {
-    case DGS_GAUSSIAN: return dispatch_d<0>(a, bwd);
-    case DGS_DERIVATIVE: return dispatch_d<1>(a, bwd);
-    case DGS_LAPLACIAN: return dispatch_d<2>(a, bwd);
-    default: return dispatch_d<3>(a, bwd);
+    case DGS_GAUSSIAN: return dispatch_d<0>(a, kind);
+    case DGS_DERIVATIVE: return dispatch_d<1>(a, kind);
+    case DGS_LAPLACIAN: return dispatch_d<2>(a, kind);
+    default: return dispatch_d<3>(a, kind);
     }
 }
 
@@ -2108,7 +2448,7 @@ extern "C" int dgs_sample_forward_ex(int mask, int P, int D, int N, int C, const
            static_cast<const char *>(binning), static_cast<const char *>(sample_binning),
            binning_bytes, sample_binning_bytes, o, nullptr, nullptr, nullptr,
            static_cast<char *>(workspace), workspace_bytes, reinterpret_cast<hipStream_t>(stream), debug};
-    return dispatch(a, false);
+    return dispatch(a, kFwd);
 }
 
 extern "C" int dgs_sample_backward_ex(int mask, int P, int D, int N, int C, const float *means,
@@ -2147,7 +2487,47 @@ extern "C" int dgs_sample_backward_ex(int mask, int P, int D, int N, int C, cons
            static_cast<const char *>(binning), static_cast<const char *>(sample_binning),
            binning_bytes, sample_binning_bytes, Outs{{nullptr, nullptr, nullptr, nullptr}},
            dL_dmeans, dL_dvalues, dL_dconics, static_cast<char *>(workspace), workspace_bytes, s, debug};
-    return dispatch(a, true);
+    return dispatch(a, kBwd);
+}
+
+extern "C" size_t dgs_sample_grad_workspace_size(int mask, int P, int D, int N, int C) {
+    const int FN = mask_code(mask);
+    if (FN < 0 || P <= 0 || N <= 0 || C <= 0 || (D != 1 && D != 2)) return 256;
+    return sgrad_layout(FN, P, D, N, C).total;
+}
+
+extern "C" int dgs_sample_backward_samples(int mask, int P, int D, int N, int C, const float *means,
+                                           const float *values, const float *conics, const float *samples,
+                                           const float *const *dL_douts, const void *binning, size_t binning_bytes,
+                                           const void *sample_binning, size_t sample_binning_bytes,
+                                           float *dL_dsamples, void *workspace, size_t workspace_bytes,
+                                           const dgs_sample_options *opts, dgs_stream_t stream, int debug) {
+    const int FN = mask_code(mask);
+    if (FN < 0) return fail(DGS_ERR_ARG, "function mask must be in 1..15");
+    // (validated with the row format the call packs: the raw conic is in every row)
+    int rc = validate(FN == 0 ? 1 : FN, P, D, N, C, binning, binning_bytes, sample_binning, sample_binning_bytes,
+                      dgs_sample_grad_workspace_size(mask, P, D, N, C), workspace_bytes);
+    if (rc) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (N == 0) return DGS_OK;
+    if (!dL_dsamples) return fail(DGS_ERR_ARG, "missing dL_dsamples");
+    // samples outside every tile (in no unit) keep this zero
+    DGS_TRY_HIP(hipMemsetAsync(dL_dsamples, 0, sizeof(float) * (size_t)N * D, s));
+    if (P == 0 || C == 0) return DGS_OK;
+    DLs d{{nullptr, nullptr, nullptr, nullptr}};
+    for (int f = 0; f < 4; ++f) {
+        if (!(mask & (1 << f))) continue;
+        if (!dL_douts || !dL_douts[f]) return fail(DGS_ERR_ARG, "missing dL_dout for a function of the mask");
+        d.p[f] = dL_douts[f];
+    }
+    const uint32_t flags = opts && !debug ? opts->flags : 0u;
+    if ((flags & DGS_SAMPLE_GRAPH_CAPTURE) && !(flags & DGS_SAMPLE_INPUTS_BINNED))
+        return fail(DGS_ERR_ARG, "DGS_SAMPLE_GRAPH_CAPTURE requires DGS_SAMPLE_INPUTS_BINNED (the binned tensors)");
+    Call a{FN, P, D, N, C, flags, means, values, conics, samples, d,
+           static_cast<const char *>(binning), static_cast<const char *>(sample_binning),
+           binning_bytes, sample_binning_bytes, Outs{{nullptr, nullptr, nullptr, nullptr}},
+           dL_dsamples, nullptr, nullptr, static_cast<char *>(workspace), workspace_bytes, s, debug};
+    return dispatch(a, kSampleGrad);
 }
 
 extern "C" int dgs_sample_forward(int function, int P, int D, int N, int C, const float *means,

@@ -559,6 +559,66 @@ Grads SampleGaussiansMultiBackward(const std::vector<int64_t> &functions, const 
     return backward_mask(mask, means_in, values_in, conics_in, samples_in, ptr, binning_in, sbinning_in, debug);
 }
 
+// dL/dsamples [N, D] of the given functions' summed loss (dgs_sample_backward_samples): `grads`
+// holds one dL_dout per function code, in that order.  Several functions at D = 2, C = 1 share
+// one traversal; otherwise the per-function calls run in turn and their gradients are added.
+// The call-time inputs are compared with the binned ones as in the other backward bindings.
+Tensor SampleGaussiansSamplesBackward(const std::vector<int64_t> &functions, const Tensor &means_in,
+                                      const Tensor &values_in, const Tensor &conics_in,
+                                      const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
+                                      const Tensor &binning_in, const Tensor &sbinning_in, const bool debug) {
+    const int mask = function_mask(functions);
+    TORCH_CHECK(dLs_in.size() == functions.size(), "one dL_dout per sampling function");
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const int P = (int)means.size(0), D = (int)means.size(-1), N = (int)samples.size(0);
+    const int C = (int)values.size(-1);
+    TORCH_CHECK(D == 1 || D == 2, "the sample gradient supports D = 1 and D = 2");
+    Tensor out = torch::zeros({N, D}, means.options());
+    if (P == 0 || N == 0 || C == 0) return out;
+    const Tensor gb = u8(binning_in, "binning_buffer"), sb = u8(sbinning_in, "sample_binning_buffer");
+    dgs_sample_options o{};
+    const bool cap = capturing();
+    if (inputs_binned(binning_in, means_in, conics_in, samples_in)) o.flags |= DGS_SAMPLE_INPUTS_BINNED;
+    else TORCH_CHECK(!cap, "sample_gaussians samples backward: ", kCaptureMsg);
+    if (cap) o.flags |= DGS_SAMPLE_GRAPH_CAPTURE;
+    std::vector<Tensor> dLs;
+    for (size_t i = 0; i < functions.size(); ++i) {
+        int64_t K = 1;
+        for (int k = 0; k < (int)functions[i]; ++k) K *= D;
+        dLs.push_back(f32(dLs_in[i], "dL_dout_values"));
+        TORCH_CHECK(dLs.back().numel() == (int64_t)N * K * C, "dL_dout has the wrong number of elements");
+    }
+    const auto run = [&](int m, const float *const *ptr, Tensor &dst) {
+        const size_t ws = dgs_sample_grad_workspace_size(m, P, D, N, C);
+        Tensor work = torch::empty({(int64_t)ws}, means.options().dtype(torch::kUInt8));
+        check(dgs_sample_backward_samples(m, P, D, N, C, means.data_ptr<float>(), values.data_ptr<float>(),
+                                          conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, gb.data_ptr(),
+                                          (size_t)gb.numel(), sb.data_ptr(), (size_t)sb.numel(),
+                                          dst.data_ptr<float>(), work.data_ptr(), (size_t)work.numel(), &o,
+                                          as_dgs(cur_stream()), debug ? 1 : 0),
+              "sample_gaussians_samples_backward");
+    };
+    if (functions.size() == 1 || (D == 2 && C == 1)) {
+        const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (size_t i = 0; i < functions.size(); ++i) ptr[functions[i]] = dLs[i].data_ptr<float>();
+        run(mask, ptr, out);
+        return out;
+    }
+    for (size_t i = 0; i < functions.size(); ++i) {
+        const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        ptr[functions[i]] = dLs[i].data_ptr<float>();
+        if (i == 0) {
+            run(1 << functions[i], ptr, out);
+        } else {
+            Tensor part = torch::empty({N, D}, means.options());
+            run(1 << functions[i], ptr, part);
+            out.add_(part);
+        }
+    }
+    return out;
+}
+
 // Diagnostics: (W_cand, W_live) over the pairs the forward evaluates.
 std::tuple<int64_t, int64_t> CountPairs(const Tensor &means_in, const Tensor &conics_in,
                                         const Tensor &samples_in, const Tensor &binning_in,
@@ -1010,6 +1070,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("count_pairs", &CountPairs);
     m.def("sample_gaussians_multi", &SampleGaussiansMulti);
     m.def("sample_gaussians_multi_backward", &SampleGaussiansMultiBackward);
+    m.def("sample_gaussians_samples_backward", &SampleGaussiansSamplesBackward);
     m.def("tile_grid", &TileGrid);
     m.def("exchange_sets", &ExchangeSets);
     m.def("inputs_match", &InputsMatch);

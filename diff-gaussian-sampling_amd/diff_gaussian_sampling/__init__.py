@@ -62,7 +62,8 @@ def sample_gaussians_multi(functions, means, values, conics, samples, num_render
     reference API).  `functions` is a sequence of names from FUNCTIONS
     ("gaussian", "derivative", "laplacian", "third"), each at most once; returns their
     outputs in that order, equal to the per-function calls within the parity tolerance.
-    Gradients flow to (means, values, conics) as the sum over the returned outputs' losses.
+    Gradients flow to (means, values, conics) -- and to samples, when they require one -- as the
+    sum over the returned outputs' losses.
     Several functions at D = 2, C = 1 share the traversal; otherwise the per-function kernels
     run in turn."""
     codes = tuple(FUNCTIONS[f] if isinstance(f, str) else int(f) for f in functions)
@@ -197,14 +198,29 @@ def call_forward(ctx, func, name, *args):
     return out
 
 
-def call_backward(ctx, func, grad_out, name):
+def _samples_backward(ctx, codes, grads, means, values, conics, samples, binning_buffer,
+                      sample_binning_buffer, name):
+    """dL/dsamples [N, D] of the functions `codes` (not on the reference, which returns None for
+    samples): the binned pair set is a function of wrap(mean - sample), so each pair's sample
+    gradient is the negative of its mean gradient."""
+    return call_debug(_C.sample_gaussians_samples_backward, ctx.debug, name, list(codes), means, values,
+                      conics, samples, [g.contiguous() for g in grads], binning_buffer,
+                      sample_binning_buffer, ctx.debug)
+
+
+def call_backward(ctx, func, grad_out, name, code):
     (means, values, conics, samples, binning_buffer, sample_binning_buffer, ranges,
      sample_ranges) = ctx.saved_tensors
     args = (means, values, conics, samples, ctx.num_rendered, grad_out, binning_buffer,
             sample_binning_buffer, ranges, sample_ranges, ctx.debug)
     grad_means, grad_values, grad_conics = call_debug(func, ctx.debug, name, *args)
-    # gradients for (means, values, conics); None for the remaining inputs (py:114-126)
-    return (grad_means, grad_values, grad_conics) + (None,) * 8
+    # gradients for (means, values, conics); None for the remaining inputs (py:114-126) --
+    # but for samples (index 3), when they require one
+    grad_samples = None
+    if ctx.needs_input_grad[3]:
+        grad_samples = _samples_backward(ctx, (code,), (grad_out,), means, values, conics, samples,
+                                         binning_buffer, sample_binning_buffer, name + "_samples")
+    return (grad_means, grad_values, grad_conics, grad_samples) + (None,) * 7
 
 
 class _SampleGaussians(torch.autograd.Function):
@@ -214,7 +230,7 @@ class _SampleGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return call_backward(ctx, _C.sample_gaussians_backward, grad_out, "bw")
+        return call_backward(ctx, _C.sample_gaussians_backward, grad_out, "bw", 0)
 
 
 class _SampleGaussiansDerivative(torch.autograd.Function):
@@ -224,7 +240,7 @@ class _SampleGaussiansDerivative(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return call_backward(ctx, _C.sample_gaussians_derivative_backward, grad_out, "der_bw")
+        return call_backward(ctx, _C.sample_gaussians_derivative_backward, grad_out, "der_bw", 1)
 
 
 class _SampleGaussiansLaplacian(torch.autograd.Function):
@@ -234,7 +250,7 @@ class _SampleGaussiansLaplacian(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return call_backward(ctx, _C.sample_gaussians_laplacian_backward, grad_out, "lap_bw")
+        return call_backward(ctx, _C.sample_gaussians_laplacian_backward, grad_out, "lap_bw", 2)
 
 
 class _SampleGaussiansMulti(torch.autograd.Function):
@@ -256,7 +272,11 @@ class _SampleGaussiansMulti(torch.autograd.Function):
         gm, gv, gc = call_debug(_C.sample_gaussians_multi_backward, ctx.debug, "multi_bw",
                                 [c for c, _ in live], means, values, conics, samples,
                                 [g for _, g in live], binning_buffer, sample_binning_buffer, ctx.debug)
-        return (None, gm, gv, gc) + (None,) * 7
+        gs = None
+        if ctx.needs_input_grad[4]:
+            gs = _samples_backward(ctx, [c for c, _ in live], [g for _, g in live], means, values, conics,
+                                   samples, binning_buffer, sample_binning_buffer, "multi_bw_samples")
+        return (None, gm, gv, gc, gs) + (None,) * 6
 
 
 class _SampleGaussiansThirdDerivative(torch.autograd.Function):
@@ -266,7 +286,7 @@ class _SampleGaussiansThirdDerivative(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        return call_backward(ctx, _C.sample_gaussians_third_derivative_backward, grad_out, "3_bw")
+        return call_backward(ctx, _C.sample_gaussians_third_derivative_backward, grad_out, "3_bw", 3)
 
 
 class _AggregateNeighbors(torch.autograd.Function):

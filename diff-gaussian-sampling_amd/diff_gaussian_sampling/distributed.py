@@ -84,6 +84,9 @@ class _ShardedSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, function, comm, means, values, conics, samples, num_rendered, binning,
                 sample_binning, ranges, sample_ranges, debug):
+        if ctx.needs_input_grad[5]:  # (the sample-position gradient is GaussianSampler's: DESIGN.md 4.9)
+            raise NotImplementedError("the sharded samplers return no gradient for samples; "
+                                      "use GaussianSampler, or detach the samples")
         fwd = getattr(_C, _FWD[function])
         out = call_debug(fwd, debug, "shard_fw", means, values, conics, samples, num_rendered,
                          binning, sample_binning, ranges, sample_ranges, debug)
@@ -574,6 +577,9 @@ class _SpatialSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, function, xchg, means, values, conics, samples, num_rendered, binning,
                 sample_binning, ranges, sample_ranges, debug):
+        if ctx.needs_input_grad[5]:  # (the sample-position gradient is GaussianSampler's: DESIGN.md 4.9)
+            raise NotImplementedError("the sharded samplers return no gradient for samples; "
+                                      "use GaussianSampler, or detach the samples")
         fwd = getattr(_C, _FWD[function])
         out = call_debug(fwd, debug, "spatial_fw", means, values, conics, samples, num_rendered,
                          binning, sample_binning, ranges, sample_ranges, debug)

@@ -30,6 +30,8 @@ def preprocess_volume(means, conics, samples, debug=False):
 class _SampleVolume(torch.autograd.Function):
     @staticmethod
     def forward(ctx, function, means, values, conics, samples, binning, debug):
+        if ctx.needs_input_grad[4]:  # (the sample-position gradient is D = 1 / 2 only: DESIGN.md 4.9)
+            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them")
         out = call_debug(_C.volume_forward, debug, "vol_fw", function, means, values, conics, samples,
                          binning, debug)
         ctx.function, ctx.debug = function, debug

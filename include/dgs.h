@@ -97,7 +97,9 @@ int dgs_preprocess(int P, int D, int N, const float *means, const float *covaria
 
 /* The ABI this header describes (dgs_version() returns it).  11: dgs_bin_options starts with
  * struct_size and flags; dgs_binning_info writes 6 values.  12: dgs_bin_options.samples_binned,
- * dgs_preprocess_auto_ex, dgs_sample_reuse_count. */
+ * dgs_preprocess_auto_ex, dgs_sample_reuse_count.  (dgs_sample_grad_workspace_size and
+ * dgs_sample_backward_samples were added at 12 too: new exported functions change no existing
+ * layout or signature, so the number stays.) */
 #define DGS_ABI_VERSION 12
 
 /* dgs_bin_options.flags */
@@ -312,6 +314,23 @@ int dgs_sample_backward_ex(int mask, int P, int D, int N, int C, const float *me
                            const void *sample_binning, size_t sample_binning_bytes, float *dL_dmeans,
                            float *dL_dvalues, float *dL_dconics, void *workspace, size_t workspace_bytes,
                            const dgs_sample_options *opts, dgs_stream_t stream, int debug);
+
+/* The gradient with respect to the sample positions (not on the reference API, which returns
+ * none).  In the binned pair set every output is a function of X = wrap(mean - sample), so a
+ * pair's dL/dsample is the negative of its dL/dmean; the wrap counts as the identity's slope and
+ * the pair set is held fixed, as in the backward.  mask and dL_douts as in dgs_sample_backward_ex
+ * (a multi-bit mask needs D = 2 and C = 1: DGS_ERR_ARG otherwise); dL_dsamples[N][D] is
+ * overwritten, and is 0 for samples outside every tile and for P = 0.  A per-sample gather: no
+ * atomics, equal bit for bit across runs.  workspace >= dgs_sample_grad_workspace_size(...); opts
+ * as in dgs_sample_backward_ex (no host sync, allocation or event under
+ * DGS_SAMPLE_GRAPH_CAPTURE; inputs that differ from the binned ones take the call-time path). */
+size_t dgs_sample_grad_workspace_size(int mask, int P, int D, int N, int C);
+int dgs_sample_backward_samples(int mask, int P, int D, int N, int C, const float *means,
+                                const float *values, const float *conics, const float *samples,
+                                const float *const *dL_douts, const void *binning, size_t binning_bytes,
+                                const void *sample_binning, size_t sample_binning_bytes,
+                                float *dL_dsamples, void *workspace, size_t workspace_bytes,
+                                const dgs_sample_options *opts, dgs_stream_t stream, int debug);
 
 /* Diagnostics (not on the reference API): counts, over the pairs the forward evaluates,
  * W_cand (candidate pairs after culling) and W_live (pairs with power >= thr, the survey's

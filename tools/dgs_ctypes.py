@@ -181,6 +181,31 @@ def sample_gaussians_multi_backward(codes, means, values, conics, samples, dLs, 
                                           int(bool(debug))))
     return dm, dv, dc
 
+
+_lib.dgs_sample_grad_workspace_size.restype = _SZ
+_lib.dgs_sample_grad_workspace_size.argtypes = [_I] * 5
+_lib.dgs_sample_backward_samples.argtypes = [_I] * 5 + [_P] * 4 + [_P, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _I]
+
+
+def sample_gaussians_samples_backward(codes, means, values, conics, samples, dLs, binning,
+                                      sample_binning, debug):
+    """dL/dsamples [N, D] of sum_f <dLs[f], out_f> for the functions `codes`
+    (dgs_sample_backward_samples; several functions: D = 2, C = 1)."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    dLs = {c: _f32(d) for c, d in zip(codes, dLs)}
+    P, D = means.shape
+    N, C = samples.shape[0], values.shape[1]
+    mask = sum(1 << c for c in codes)
+    ds = torch.zeros(N, D, device=means.device)
+    ptrs = _PP(*[dLs[c].data_ptr() if c in dLs else None for c in range(4)])
+    ws = torch.empty(_lib.dgs_sample_grad_workspace_size(mask, P, D, N, C), dtype=torch.uint8,
+                     device=means.device)
+    _check(_lib.dgs_sample_backward_samples(mask, P, D, N, C, _ptr(means), _ptr(values), _ptr(conics),
+                                            _ptr(samples), ptrs, _ptr(binning), binning.numel(),
+                                            _ptr(sample_binning), sample_binning.numel(), _ptr(ds),
+                                            _ptr(ws), ws.numel(), None, _stream(), int(bool(debug))))
+    return ds
+
 # ---- neighbour aggregation (aggregate_neighbors.h:11-47) ---------------------------------
 _lib.dgs_agg_preprocess.argtypes = [_I, _I, _P, _P, _P, _P, _P, _P, ALLOC_FN, _P, ctypes.POINTER(_I64), _P, _I]
 _lib.dgs_agg_forward.argtypes = [_I] * 5 + [_P] * 11 + [_P] + [_P] * 4 + [_P, _I]
