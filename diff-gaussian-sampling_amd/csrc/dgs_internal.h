@@ -34,8 +34,28 @@ constexpr int64_t kMaxGaussians = (int64_t)kIdMask;
 // Culling threshold on q = X^T A X.  power = -q/2 < -105 makes expf(power) exactly +0 in
 // fp32 (e^-105 < half of the smallest subnormal), so every forward and backward term of such
 // a pair is exactly zero in the reference (all of them carry the factor G); culling them
-// is result-preserving.
+// is result-preserving.  kQCut is the cut of everything that may evaluate a pair with expf (the
+// call-time path, kUnsafe entries, torus-shifted images -- they can become kUnsafe at a wrap
+// breakpoint), of the exchange sets and of the eligibility tests (Cut::cull).
 constexpr double kQCut = 210.0;
+// The cut of entries only the fast paths evaluate (flag-free entries of a positive-definite conic
+// below kRho2Max, the k = 0 image).  Those paths form G with one bare v_exp_f32 (fast_exp2,
+// dgs_render.h), which delivers no subnormal result: it returns exactly +0 for every input below
+// kExp2FlushBelow = -126 (measured over every float of [-160, -120] on gfx950,
+// tests/test_gpu_flush_cut.py, profiles/r07_exp2_probe.json), so G -- a factor of every forward and
+// backward term -- is already an exact zero there, whatever q.  The exact log2 exponent of a pair
+// is -(log2 e / 2) q.  Every fast path computes it in fp32 in its own operation order (forward
+// fma form, backward monomial form, the matrix-core and moment forms, D = 1) with the error of
+// the note at kRho2Max below: |error| <~ 3e-7 A q in natural units, 3e-7 A q log2 e here, with the
+// amplification A = (1 + rho) / (1 - rho) < 8000 for rho^2 < kRho2Max.  So the computed exponent
+// of a pair with q > kQCutFast is below
+//   -(log2 e / 2) kQCutFast (1 - 2 x 3e-7 x 8000) = -0.72135 x 176 x 0.9952 = -126.35 < -126:
+// culling it drops a hardware zero.  (The smallest such cut is 126 / (0.72135 x 0.9952) = 175.51;
+// 176 leaves 0.35 in the exponent, i.e. 0.49 in q, for the rounding of X = m - s.)
+constexpr double kExp2FlushBelow = -126.0;
+constexpr double kQCutFast = 176.0;
+static_assert(-0.5 * 1.4426950408889634 * kQCutFast * (1.0 - 2.0 * 3e-7 * 8000.0) < kExp2FlushBelow - 0.25,
+              "kQCutFast: the computed exponent of a culled pair must stay below the flush threshold");
 constexpr double kCellSlack = 1e-3;  // fraction of a fine cell tolerated outside its bounds
 constexpr int kWave = 64;
 // Forward work unit: a block of up to 32 sample PAIRS of one cell, pair-aligned in the sorted
@@ -496,6 +516,8 @@ struct Geom {
     float off[2];
     double fs;   // fine cell size = 0.51f / n
     double ifs;  // 1 / fs (the binning's cell indices multiply by it: no fp64 divisions)
+    double qf;   // the cut of fast-path-only entries: kQCutFast, or kQCut (DGS_BIN_QCUT_REFERENCE)
+    double rf;   // sqrt(qf / kQCut): that cut's half-widths over the reference cut's (1 when qf == kQCut)
 };
 
 __device__ inline uint32_t sample_cell(const Geom &G, const float *s) {

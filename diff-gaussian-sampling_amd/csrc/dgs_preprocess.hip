@@ -6,8 +6,10 @@
 // reference tile membership is reproduced exactly (radius, rect, torus wrap, clamp rules;
 // num_rendered, radii, ranges are bit-identical), and each tile is refined into fine cells:
 // a Gaussian is listed in a cell only if some sample of the cell can see a non-zero
-// contribution (q = X^T A X <= 210, i.e. expf(power) != 0 in fp32).  Culled pairs are
-// exactly-zero pairs of the reference, so the sums are unchanged.
+// contribution: q = X^T A X <= 210, i.e. expf(power) != 0 in fp32, for entries the literal path
+// may evaluate; q <= 176 for entries only the fast paths evaluate, whose bare v_exp_f32 returns +0
+// beyond that (kQCutFast, dgs_internal.h).  Culled pairs are exactly-zero terms of this
+// implementation, so the sums are unchanged.
 //
 // Work lists produced here (see dgs_internal.h for the layout):
 //   * samples sorted by fine cell, per-cell sample ranges, forward work units (cell, 64 samples)
@@ -403,7 +405,10 @@ __device__ inline bool box_hits_ellipse(double xa, double xb, double ya, double 
 // the sort path) and the per-cell gather (k_gather): both must take the same decisions bit for
 // bit, so these helpers run with contraction off.
 struct Cut {
-    double e[2], md[2], epsx[2], c0, c1, c2;
+    // e: half-widths of the reference cut kQCut (eligibility, shifted images, anything that may
+    // become kUnsafe); ef: those of the fast cut G.qf, for visits whose entries only the fast
+    // paths evaluate (enumerate_fine's `fast` visits, local_rows); ef <= e, and ef == e bit for bit when G.qf == kQCut
+    double e[2], ef[2], md[2], epsx[2], c0, c1, c2;
     bool pd, cull;
 };
 
@@ -430,6 +435,8 @@ __device__ __forceinline__ Cut gauss_cut(const Geom &G, const float *m, const fl
         }
     }
     k.cull = k.pd && k.e[0] < 0.5 && (D == 1 || k.e[1] < 0.5);
+    k.ef[0] = k.e[0] * G.rf;
+    k.ef[1] = k.e[1] * G.rf;
     for (int d = 0; d < 2; ++d) {
         k.md[d] = d < D ? (double)m[d] - (double)G.off[d] : 0.0;
         k.epsx[d] = 1e-6 * (1.0 + fabs((double)m[d]) + fabs((double)G.off[d]));
@@ -463,6 +470,22 @@ __device__ __forceinline__ bool axis_setup(const Geom &G, const Cut &k, int d, i
     return flo <= fhi;
 }
 
+// A local visit (visit_local: the k = 0 image, |X| < 1 in every cell it meets) of a conic that is
+// not kUnsafe emits flag-free entries only -- evaluated by the fast paths alone, whose G is a
+// hardware zero beyond G.qf (dgs_internal.h, kQCutFast): its cells are those of the fast cut.
+// Narrows axis d's range [flo, fhi] of axis_setup (ks = 0) to it; false if none is left.
+__device__ __forceinline__ bool axis_fast(const Geom &G, const Cut &k, int d, int tcd, int &flo, int &fhi) {
+    DGS_CUT_CONTRACT
+    const double o = tcd * (double)kTile;
+    const double dl = k.md[d] - k.ef[d] - k.epsx[d];
+    const double dh = k.md[d] + k.ef[d] + k.epsx[d];
+    const int lo = (int)floor(fmax((dl - o) * G.ifs - kCellSlack, -1.0));
+    const int hi = (int)floor(fmin((dh - o) * G.ifs + kCellSlack, (double)G.n));
+    flo = max(flo, lo);
+    fhi = min(fhi, hi);
+    return flo <= fhi;
+}
+
 // The row's cells that meet the ellipse X^T A X <= q (D = 2, culled): project the ellipse's
 // slice over the row's X1 band onto X0 (a slice of a convex set is convex, so "box meets
 // ellipse" <=> the cell's X0 range meets that interval), in fp32 with local_rows' construction
@@ -474,25 +497,32 @@ __device__ __forceinline__ bool axis_setup(const Geom &G, const Cut &k, int d, i
 // holds three quarters of the entries.)  Per Gaussian init(); per row cols() narrows [fxl, fxh]
 // for the visit whose tile-relative mean (torus shift included) is (md0, md1).
 struct Slice32 {
-    float qcc0, c1, det, ic0, yu0, yl0, e1, eps0, eps1, tol0, fs, ifs, slack;
+    // (r*: the reference cut kQCut; f*: the fast cut G.qf of fast-path-only visits)
+    float rqcc0, ryu0, re1, rtol0, fqcc0, fyu0, fe1, ftol0;
+    float c1, det, ic0, eps0, eps1, fs, ifs, slack;
     __device__ __forceinline__ void init(const Geom &G, const Cut &k) {
-        const float qc = (float)(kQCut * (1.0 + 1e-6));
-        const float c0f = (float)k.c0, c2f = (float)k.c2, e0 = (float)k.e[0];
+        const float qc = (float)(kQCut * (1.0 + 1e-6)), qcf = (float)(G.qf * (1.0 + 1e-6));
+        const float c0f = (float)k.c0, c2f = (float)k.c2, e0 = (float)k.e[0], e0f = (float)k.ef[0];
         c1 = (float)k.c1;
         det = (float)(k.c0 * k.c2 - k.c1 * k.c1);
         ic0 = 1.0f / c0f;
-        yu0 = -c1 * e0 / c2f;
-        yl0 = c1 * e0 / c2f;
-        qcc0 = qc * c0f;
-        e1 = (float)k.e[1];
+        ryu0 = -c1 * e0 / c2f;
+        fyu0 = -c1 * e0f / c2f;
+        rqcc0 = qc * c0f;
+        fqcc0 = qcf * c0f;
+        re1 = (float)k.e[1];
+        fe1 = (float)k.ef[1];
         eps0 = (float)k.epsx[0] + 1e-6f;
         eps1 = (float)k.epsx[1] + 1e-6f;
-        tol0 = 2e-3f * e0 + 1e-5f;
+        rtol0 = 2e-3f * e0 + 1e-5f;
+        ftol0 = 2e-3f * e0f + 1e-5f;
         fs = (float)G.fs;
         ifs = (float)G.ifs;
         slack = (float)(kCellSlack * G.fs);
     }
-    __device__ __forceinline__ bool cols(int fy, float md0, float md1, int n, int &fxl, int &fxh) const {
+    __device__ __forceinline__ bool cols(int fy, float md0, float md1, int n, int &fxl, int &fxh, bool fast) const {
+        const float qcc0 = fast ? fqcc0 : rqcc0, yu0 = fast ? fyu0 : ryu0, yl0 = -yu0;
+        const float e1 = fast ? fe1 : re1, tol0 = fast ? ftol0 : rtol0;
         const float ya = fmaxf(md1 - ((float)(fy + 1) * fs + slack) - eps1, -e1);
         const float yb = fminf(md1 - ((float)fy * fs - slack) + eps1, e1);
         if (!(ya <= yb)) return false;
@@ -601,6 +631,12 @@ __device__ __forceinline__ void enumerate_fine(const Geom &G, const float *m, fl
             bool any = axis_setup(G, k, 0, tc[0], ks[0], flo[0], fhi[0]);
             if (any && D == 2) any = axis_setup(G, k, 1, tc[1], ks[1], flo[1], fhi[1]);
             const bool local = visit_local(G, k, ks);
+            // (entries of such a visit are flag-free: only the fast paths evaluate them)
+            const bool fast = local && !uflag;
+            if (any && fast) {
+                any = axis_fast(G, k, 0, tc[0], flo[0], fhi[0]);
+                if (any && D == 2) any = axis_fast(G, k, 1, tc[1], flo[1], fhi[1]);
+            }
             // (k_gather makes the direct -- unwrapped -- local visits of a regular Gaussian)
             const bool direct = x >= 0 && x < G.grid[0] && (D == 1 || (y >= 0 && y < G.grid[1]));
             if (any && !(skip_local && local && direct)) {
@@ -611,7 +647,7 @@ __device__ __forceinline__ void enumerate_fine(const Geom &G, const float *m, fl
                 const float md1 = (float)(k.md[1] - tc[1] * (double)kTile - 2.0 * ks[1]);
                 for (int fy = ylo; fy <= yhi; ++fy) {
                     int fxl = flo[0], fxh = fhi[0];
-                    if (k.cull && D == 2 && !sl.cols(fy, md0, md1, G.n, fxl, fxh)) continue;
+                    if (k.cull && D == 2 && !sl.cols(fy, md0, md1, G.n, fxl, fxh, fast)) continue;
                     for (int fx = fxl; fx <= fxh; ++fx) {
                         const uint32_t cell = base + (uint32_t)(fy * G.n + fx);
                         // Empty cells get no units: an entry there would never be read, and its
@@ -622,7 +658,8 @@ __device__ __forceinline__ void enumerate_fine(const Geom &G, const float *m, fl
                             const double o = tc[0] * (double)kTile;
                             const double dlo = o + fx * G.fs - slack, dhi = o + (fx + 1) * G.fs + slack;
                             const double xa = k.md[0] - dhi - k.epsx[0], xb = k.md[0] - dlo + k.epsx[0];
-                            if (!(xa - 2.0 * ks[0] <= k.e[0] && xb - 2.0 * ks[0] >= -k.e[0])) continue;
+                            const double ee = fast ? k.ef[0] : k.e[0];
+                            if (!(xa - 2.0 * ks[0] <= ee && xb - 2.0 * ks[0] >= -ee)) continue;
                         }
                         // Wrap class from the cell's actual samples (box = their bounding box;
                         // the nominal cell may reach past the last sample): kGeneral when some
@@ -702,7 +739,10 @@ __device__ __forceinline__ bool local_rows(const Geom &G, const KeyRect &kr, con
         const int tx = ta + t;
         if (tx > tb) break;
         int ks[2] = {0, 0};
-        if (axis_setup(G, k, 0, tx, ks[0], xlo[t], xhi[t]) && visit_local(G, k, ks)) continue;
+        // (every visit made here is local and the conic is not kUnsafe -- gather_reach --: the fast cut)
+        if (axis_setup(G, k, 0, tx, ks[0], xlo[t], xhi[t]) && visit_local(G, k, ks) &&
+            axis_fast(G, k, 0, tx, xlo[t], xhi[t]))
+            continue;
         xlo[t] = 1; xhi[t] = 0;
     }
     if (tb > ta + 1) return false;  // (wider than two tiles: not for this path)
@@ -711,15 +751,15 @@ __device__ __forceinline__ bool local_rows(const Geom &G, const KeyRect &kr, con
     // -- the slice ends' error is at most ~sqrt(8 eps) of the cut's half-width where the sqrt
     // argument cancels (the ellipse's top and bottom), so tol = 2e-3 e0 + 1e-5 (1 + |x|) in
     // displacement units, a few thousandths of a cell.  Extra cells only add exact zeros.
-    const float qc = (float)(kQCut * (1.0 + 1e-6));
+    const float qc = (float)(G.qf * (1.0 + 1e-6));
     const float c0 = (float)k.c0, c1 = (float)k.c1, c2 = (float)k.c2;
     const float det = (float)(k.c0 * k.c2 - k.c1 * k.c1);
-    // (e0: the cut's X0 half-width; k.e[0] exceeds sqrt(qc c2 / det) by ~5e-7 relative, which
+    // (e0: the cut's X0 half-width; k.ef[0] exceeds sqrt(qc c2 / det) by ~5e-7 relative, which
     // only widens the slices)
-    const float e0 = (float)k.e[0], ic0 = 1.0f / c0;
+    const float e0 = (float)k.ef[0], ic0 = 1.0f / c0;
     const float yu0 = -c1 * e0 / c2, yl0 = c1 * e0 / c2, qcc0 = qc * c0;
     const float fs = (float)G.fs, ifsf = (float)G.ifs, slackf = (float)slack;
-    const float e1 = (float)k.e[1], eps1 = (float)k.epsx[1] + 1e-6f, eps0 = (float)k.epsx[0] + 1e-6f;
+    const float e1 = (float)k.ef[1], eps1 = (float)k.epsx[1] + 1e-6f, eps0 = (float)k.epsx[0] + 1e-6f;
     const float tol0 = 2e-3f * e0 + 1e-5f;
     float A0[2], B0[2];  // per tile of the x range: the tile-relative mean +- the margins
     for (int t = 0; t < 2; ++t) {
@@ -733,7 +773,7 @@ __device__ __forceinline__ bool local_rows(const Geom &G, const KeyRect &kr, con
     const float fn = (float)G.n;
     for (int ty = max(kr.y0, 0); ty < min(kr.y1, G.grid[1]); ++ty) {  // direct visits only
         int ks1, flo1, fhi1;
-        if (!axis_setup(G, k, 1, ty, ks1, flo1, fhi1) || ks1 != 0) continue;
+        if (!axis_setup(G, k, 1, ty, ks1, flo1, fhi1) || ks1 != 0 || !axis_fast(G, k, 1, ty, flo1, fhi1)) continue;
         const float md1 = (float)(k.md[1] - ty * BS);
         // (the row body without branches: its divergent continues / breaks were a third of
         // this kernel's instructions; partial stores of a Gaussian that ends up `bad` are never
@@ -1340,7 +1380,7 @@ __global__ __launch_bounds__(kBlock) void k_sub_box(int ncells, int CT, const in
 // Does the box [xa, xb] x [ya, yb] of displacements contain an X with X^T A X <= qcut?  fp32
 // with the reciprocals of c0 / c2 given (the sub-cell test runs once per entry and sub-cell).
 // Rounding moves the computed minimum by ~1e-6 relative; the callers' qcut has a 1e-4 margin and
-// the live pairs end at 207.9 (expf underflow), so a live pair is never culled.
+// the live pairs end at 207.9 (expf underflow; 175.51 on the fast paths, cut 176), so a live pair is never culled.
 __device__ inline bool box_hits_ellipse_f(float xa, float xb, float ya, float yb, float c0, float c1, float c2,
                                           float ic0, float ic2, float qcut) {
     if (xa <= 0.0f && xb >= 0.0f && ya <= 0.0f && yb >= 0.0f) return true;
@@ -1358,7 +1398,7 @@ __device__ inline bool box_hits_ellipse_f(float xa, float xb, float ya, float yb
     return best <= qcut;
 }
 
-// The sub-cells of one cell a cell-list entry's cut X^T A X <= kQCut meets (bit k = sub-cell k),
+// The sub-cells of one cell a cell-list entry's cut X^T A X <= kQCut (flag-free: G.qf) meets (bit k = sub-cell k),
 // tested with the displacement the forward uses: X = m - s, minus the entry's constant wrap
 // shift for kGeneral entries (wrap_shift_f of the mean minus the cell-box centre, exactly as
 // k_forward_t forms it).  kUnsafe entries get none (the forward's tail pass adds them per cell).
@@ -1375,9 +1415,12 @@ __device__ __forceinline__ void sub_row(uint32_t ent, const float2 *__restrict__
 }
 
 __device__ __forceinline__ uint32_t sub_mask(uint32_t ent, const float2 &mm, const float4 &cc, const float4 &bx,
-                                             const float *ctr, const float4 *sb) {
+                                             const float *ctr, const float4 *sb, float qcf) {
     if (ent & kUnsafe) return 0u;
-    const float qc = (float)(kQCut * (1.0 + 1e-4));
+    // A flag-free entry (the k = 0 image, a conic that is not kUnsafe) is evaluated by the fast
+    // paths alone: the fast cut qcf = G.qf (1 + 1e-4) (dgs_internal.h, kQCutFast).  A kGeneral
+    // entry is a torus-shifted image: the reference cut.
+    const float qc = (ent & kGeneral) ? (float)(kQCut * (1.0 + 1e-4)) : qcf;
     float sh[2] = {0.0f, 0.0f};
     if (ent & kGeneral) {
         sh[0] = wrap_shift_f(mm.x - ctr[0]);
@@ -1395,8 +1438,8 @@ __device__ __forceinline__ uint32_t sub_mask(uint32_t ent, const float2 &mm, con
     // Per sub-row (the union of its two sub-boxes' sample y ranges) the ellipse's slice is one
     // X0 interval [xl, xu] (row_slice's construction in fp32); a sub-box is hit when its X0
     // range meets it.  Two slices per entry instead of four box minimisations.  The union band
-    // and the tolerances only widen the lists (the cut itself sits 1 % outside the last live
-    // pair, kQCut).
+    // and the tolerances only widen the lists (the cut itself sits outside the last live pair:
+    // kQCut by 1 %, kQCutFast by 0.3 % -- 175.51 against 176, dgs_internal.h).
     const float c0 = cc.x, c1 = cc.y, c2 = cc.z;
     const float det = c0 * c2 - c1 * c1;
     const float ex0 = __builtin_amdgcn_sqrtf(qc * c2 * __builtin_amdgcn_rcpf(det));
@@ -1446,6 +1489,7 @@ struct SubListArgs {
     const float4 *gcon, *box, *sbox;
     int32_t *lbeg, *lmid, *lend, *lthin;
     uint32_t *sub_ent;
+    float qcf;  // the flag-free entries' cut, G.qf (1 + 1e-4)
 };
 
 __device__ __forceinline__ void sub_lists_wave(const SubListArgs &A, int c, int lane) {
@@ -1497,7 +1541,7 @@ __device__ __forceinline__ void sub_lists_wave(const SubListArgs &A, int c, int 
             sub_row(ent_c, gmean, gcon, mm_c, cc_c);
             ent_n = j + 2 * kWave < e ? entries[j + 2 * kWave] : kUnsafe;
 #endif
-            const uint32_t mask = j < e ? sub_mask(ent, mm, cc, bx, ctr, sb) : 0u;
+            const uint32_t mask = j < e ? sub_mask(ent, mm, cc, bx, ctr, sb, A.qcf) : 0u;
             const bool ff = j < m_;
 #pragma unroll
             for (int k = 0; k < kSubPerCell; ++k) {
@@ -2000,6 +2044,15 @@ static void size_spec_put(int P, int N, int D, int64_t E, int64_t R) {
     g_spec.R = R;
 }
 
+// DGS_QCUT_REFERENCE=1 (read once): every binning of the process as with DGS_BIN_QCUT_REFERENCE.
+static bool qcut_reference_env() {
+    static const bool on = [] {
+        const char *e = std::getenv("DGS_QCUT_REFERENCE");
+        return e && e[0] && e[0] != '0';
+    }();
+    return on;
+}
+
 // The binning with the host-known grid `grid`/`grid_offset`.  dgrid/doff (device, optional): a
 // device-computed grid read back at the one host sync into *dev_grid / *dev_off (D entries).
 static int preprocess_body(int P, int D, int N, const float *means, const float *covariances,
@@ -2051,6 +2104,10 @@ static int preprocess_body(int P, int D, int N, const float *means, const float 
     G.ncells = (int)ncells64;
     G.fs = (double)kTile / G.n;
     G.ifs = 1.0 / G.fs;
+    // (the A/B and test knob: every entry binned with the reference cut, as before kQCutFast)
+    const bool ref_cut = (copt && (copt->flags & DGS_BIN_QCUT_REFERENCE)) || qcut_reference_env();
+    G.qf = ref_cut ? kQCut : kQCutFast;
+    G.rf = ref_cut ? 1.0 : std::sqrt(kQCutFast / kQCut);
     const int ncells = G.ncells;
     const int home_w = G.grid[0] * G.n, home_h = D == 2 ? G.grid[1] * G.n : 1;
     // an earlier binning of the same samples on this grid and these fine cells: its sample side
@@ -2547,7 +2604,8 @@ static int preprocess_body(int P, int D, int N, const float *means, const float 
         int32_t *sub_lthin = reinterpret_cast<int32_t *>(gbuf + L.o_sub_lthin);
         uint32_t *sub_ent = reinterpret_cast<uint32_t *>(gbuf + L.o_sub_ent);
         const SubListArgs sa{ncells,   G.CT,     cell_gbeg, cell_gmid, cell_gend, entries,  gmean,  gcon,
-                             cell_box, sub_box,  sub_lbeg,  sub_lmid,  sub_lend,  sub_lthin, sub_ent};
+                             cell_box, sub_box,  sub_lbeg,  sub_lmid,  sub_lend,  sub_lthin, sub_ent,
+                             (float)(G.qf * (1.0 + 1e-4))};
         k_sub_lists<<<(unsigned)((ncells + kWavesPerBlock - 1) / kWavesPerBlock), kBlock, 0, s>>>(sa);
         DGS_LAUNCH_CHECK(s, debug);
         // forward sub units per sub-cell with samples and entries: (sub-cell, kSubPairs pairs)
@@ -2667,6 +2725,8 @@ static int build_ref_lists(const Header &h, char *gbuf, hipStream_t s, int debug
     G.off[0] = h.off[0]; G.off[1] = h.off[1];
     G.fs = (double)kTile / h.n;
     G.ifs = 1.0 / G.fs;
+    G.qf = kQCut;  // (the tile lists make no cut)
+    G.rf = 1.0;
     const int rbits = bit_length((uint64_t)(G.T > 1 ? G.T - 1 : 1));
     uint32_t *rlist = reinterpret_cast<uint32_t *>(gbuf + h.o_rlist);
     const RadixPlan plan = radix_plan(R, rbits);
@@ -2798,7 +2858,7 @@ extern "C" int dgs_preprocess_ex(int P, int D, int N, const float *means, const 
     if (opts && opts->struct_size != sizeof(dgs_bin_options))
         return fail(DGS_ERR_ARG, "dgs_preprocess_ex: dgs_bin_options.struct_size must be sizeof(dgs_bin_options) "
                                  "(a caller built against another dgs.h; see DGS_ABI_VERSION)");
-    if (opts && (opts->flags & ~(uint32_t)(DGS_BIN_STATUS_STICKY | DGS_BIN_SAMPLES_FIXED)))
+    if (opts && (opts->flags & ~(uint32_t)(DGS_BIN_STATUS_STICKY | DGS_BIN_SAMPLES_FIXED | DGS_BIN_QCUT_REFERENCE)))
         return fail(DGS_ERR_ARG, "dgs_preprocess_ex: unknown dgs_bin_options.flags");
     const uint8_t *present = opts ? opts->present : nullptr;
     const double area = opts ? opts->sample_area : 0.0;
@@ -2866,7 +2926,7 @@ extern "C" int dgs_preprocess_auto_ex(int P, int D, int N, const float *means, c
     if (opts && opts->struct_size != sizeof(dgs_bin_options))
         return fail(DGS_ERR_ARG, "dgs_preprocess_auto_ex: dgs_bin_options.struct_size must be sizeof(dgs_bin_options) "
                                  "(a caller built against another dgs.h; see DGS_ABI_VERSION)");
-    if (opts && (opts->flags || opts->capacity_E > 0))
+    if (opts && ((opts->flags & ~(uint32_t)DGS_BIN_QCUT_REFERENCE) || opts->capacity_E > 0))
         return fail(DGS_ERR_ARG, "dgs_preprocess_auto_ex: flags and capacities are for dgs_preprocess_ex");
     const uint8_t *present = opts ? opts->present : nullptr;
     const double area = opts ? opts->sample_area : 0.0;

@@ -146,10 +146,20 @@ __global__ void k_pack_samples(int N, const char *__restrict__ gbuf, const char 
 // power <= 0 is guaranteed and G = 2^(power*log2e) is one v_exp_f32.  General path: the
 // reference's exact wrap and, for other conics, the reference-literal power with its
 // `power > 0 -> skip` rule (forward.cu:228) and an accurate expf.
+// (Both exponent forms below feed a bare v_exp_f32, which returns +0 below -126: the pairs beyond
+// kQCutFast are hardware zeros and not listed -- dgs_internal.h; dgs_debug_pair_probe returns
+// the exponent and G of given pairs in either form.)
 template <int D, typename V>
-__device__ __forceinline__ V fast_prob(const V *X, const float *k) {
-    if constexpr (D == 2) return vexp2(vfma(X[0], vfma(bc<V>(k[0]), X[0], k[1] * X[1]), k[2] * X[1] * X[1]));
-    else return vexp2(k[0] * X[0] * X[0]);
+__device__ __forceinline__ V fast_power(const V *X, const float *k) {  // the fma form
+    if constexpr (D == 2) return vfma(X[0], vfma(bc<V>(k[0]), X[0], k[1] * X[1]), k[2] * X[1] * X[1]);
+    else return k[0] * X[0] * X[0];
+}
+template <int D, typename V>
+__device__ __forceinline__ V fast_prob(const V *X, const float *k) { return vexp2(fast_power<D, V>(X, k)); }
+// the monomial form (the gaussian backward's: q = (X0^2, X0 X1, X1^2), the conic moments' factors)
+template <typename V>
+__device__ __forceinline__ V mono_power(const float *k, V q0, V q1, V q2) {
+    return vfma(bc<V>(k[2]), q2, vfma(bc<V>(k[1]), q1, k[0] * q0));
 }
 
 template <int FN, int D>
@@ -1230,7 +1240,7 @@ __device__ __forceinline__ void bwd_sample(const V *srow, const float *m, const 
         // gaussian, C = 1: the exponent from the quadratic monomials q = (X0^2, X0 X1, X1^2)
         // that the conic moments need anyway -- 15 packed ops per two pairs instead of 16
         const V q0 = X[0] * X[0], q1 = X[0] * X[1], q2 = X[1] * X[1];
-        const V e = vexp2(vfma(bc<V>(kk[2]), q2, vfma(bc<V>(kk[1]), q1, kk[0] * q0)));
+        const V e = vexp2(mono_power<V>(kk, q0, q1, q2));
         const V t = e * dl[0][0];
         V *gm = acc, *gv = acc + 2, *gc = acc + 3;
         gv[0] += t;
@@ -2645,6 +2655,71 @@ extern "C" int dgs_inputs_match(int P, int D, int N, const float *means, const f
     DGS_TRY_HIP(hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, s));
     DGS_TRY_HIP(hipStreamSynchronize(s));
     *match = h ? 0 : 1;
+    return DGS_OK;
+}
+
+// Test hooks of the fast cut (kQCutFast, dgs_internal.h; tests/test_gpu_flush_cut.py; not on the
+// reference API, not in include/).  dgs_debug_exp2_probe: fast_exp2 of each element.
+// dgs_debug_pair_probe: pair i = (Gaussian i, sample i) as the fast paths evaluate it -- X = m - s
+// in fp32, the pre-scaled k of k_pack_gauss, the log2 exponent in the forward's fma form
+// (form 0, fast_power) or the gaussian backward's monomial form (form 1, mono_power; D = 2), and
+// G = fast_exp2 of it.  The probe is a scalar-float kernel of its own: it shares fast_power and
+// mono_power with the render kernels, but the compiler is free to contract the products feeding
+// them differently here than in the packed instantiations of k_forward_s and k_backward, so the
+// probe shows ONE legal fp32 order of each form, not provably the kernels' own.  The cut does not
+// rest on it: the derivation at kQCutFast bounds every order.  The matrix-core form (the fmaf
+// chain of k_forward_mx / k_backward_mx) and the moment forms are covered by that bound and by
+// reading only, not probed.  dgs_debug_cut_constants: {kQCut, kQCutFast, kRho2Max, kExp2FlushBelow}.
+__global__ void k_exp2_probe(int64_t n, const float *__restrict__ x, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = fast_exp2(x[i]);
+}
+
+template <int D>
+__global__ void k_pair_probe(int64_t n, const float *__restrict__ means, const float *__restrict__ conics,
+                             const float *__restrict__ samples, int form, float *__restrict__ G,
+                             float *__restrict__ p2) {
+    constexpr int S = D * (D + 1) / 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *c = conics + i * S;
+    float X[2] = {means[i * D] - samples[i * D], 0.0f}, k[3] = {-0.5f * kLog2e * c[0], 0.0f, 0.0f};
+    if constexpr (D == 2) {
+        X[1] = means[i * D + 1] - samples[i * D + 1];
+        k[1] = -kLog2e * c[1];
+        k[2] = -0.5f * kLog2e * c[2];
+    }
+    const float p = form == 0 ? fast_power<D, float>(X, k) : mono_power<float>(k, X[0] * X[0], X[0] * X[1], X[1] * X[1]);
+    p2[i] = p;
+    G[i] = fast_exp2(p);
+}
+
+extern "C" double dgs_debug_qcut_fast(void) { return kQCutFast; }
+
+extern "C" void dgs_debug_cut_constants(double out[4]) {
+    out[0] = kQCut;
+    out[1] = kQCutFast;
+    out[2] = kRho2Max;
+    out[3] = kExp2FlushBelow;
+}
+
+extern "C" int dgs_debug_exp2_probe(int64_t n, const float *x, float *out, dgs_stream_t stream) {
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(DGS_ERR_ARG, "dgs_debug_exp2_probe: bad arguments");
+    if (n == 0) return DGS_OK;
+    k_exp2_probe<<<grid_for(n), kBlock, 0, reinterpret_cast<hipStream_t>(stream)>>>(n, x, out);
+    DGS_TRY_HIP(hipGetLastError());
+    return DGS_OK;
+}
+
+extern "C" int dgs_debug_pair_probe(int D, int64_t n, const float *means, const float *conics, const float *samples,
+                                    int form, float *G, float *p2, dgs_stream_t stream) {
+    if ((D != 1 && D != 2) || n < 0 || (form != 0 && !(form == 1 && D == 2)) || (n > 0 && (!means || !conics || !samples || !G || !p2)))
+        return fail(DGS_ERR_ARG, "dgs_debug_pair_probe: bad arguments");
+    if (n == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (D == 2) k_pair_probe<2><<<grid_for(n), kBlock, 0, s>>>(n, means, conics, samples, form, G, p2);
+    else k_pair_probe<1><<<grid_for(n), kBlock, 0, s>>>(n, means, conics, samples, form, G, p2);
+    DGS_TRY_HIP(hipGetLastError());
     return DGS_OK;
 }
 

@@ -307,6 +307,48 @@ PreprocessCapturableCUDA(const Tensor &means, const Tensor &values, const Tensor
                            status);
 }
 
+// Test / A-B surface of the fast cut (dgs.h DGS_BIN_QCUT_REFERENCE; tests/test_gpu_flush_cut.py).
+extern "C" double dgs_debug_qcut_fast(void);
+extern "C" void dgs_debug_cut_constants(double out[4]);
+extern "C" int dgs_debug_exp2_probe(int64_t n, const float *x, float *out, dgs_stream_t stream);
+extern "C" int dgs_debug_pair_probe(int D, int64_t n, const float *means, const float *conics, const float *samples,
+                                    int form, float *G, float *p2, dgs_stream_t stream);
+
+// preprocess_gaussians with the reference cut for every list entry.
+PreOut PreprocessRefCutCUDA(const Tensor &means, const Tensor &values, const Tensor &covariances,
+                            const Tensor &conics, const Tensor &samples, const bool debug) {
+    dgs_bin_options o{};
+    o.struct_size = sizeof(dgs_bin_options);
+    o.flags = DGS_BIN_QCUT_REFERENCE;
+    return preprocess_impl(means, values, covariances, conics, samples, nullptr, nullptr, debug, &o);
+}
+
+// fast_exp2 (the fast paths' bare v_exp_f32) of each element.
+Tensor Exp2Probe(const Tensor &x_in) {
+    const Tensor x = f32(x_in, "x");
+    Tensor out = torch::empty_like(x);
+    check(dgs_debug_exp2_probe(x.numel(), x.data_ptr<float>(), out.data_ptr<float>(), as_dgs(cur_stream())),
+          "exp2_probe");
+    return out;
+}
+
+// (G, log2 exponent) of pairs (Gaussian i, sample i) in the forward's (form 0) or the gaussian
+// backward's (form 1, D = 2) evaluation order.
+std::tuple<Tensor, Tensor> PairProbe(const Tensor &means_in, const Tensor &conics_in, const Tensor &samples_in,
+                                     int64_t form) {
+    const Tensor means = f32(means_in, "means"), conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    TORCH_CHECK(means.dim() == 2 && conics.dim() == 2 && samples.dim() == 2, "pair_probe: [n, D] / [n, S] tensors");
+    const int64_t n = means.size(0), D = means.size(1);
+    TORCH_CHECK((D == 1 || D == 2) && conics.size(0) == n && conics.size(1) == D * (D + 1) / 2 &&
+                    samples.size(0) == n && samples.size(1) == D,
+                "pair_probe: means [n, D], conics [n, D (D + 1) / 2], samples [n, D]");
+    Tensor G = torch::empty({n}, means.options()), p2 = torch::empty({n}, means.options());
+    check(dgs_debug_pair_probe((int)D, n, means.data_ptr<float>(), conics.data_ptr<float>(), samples.data_ptr<float>(),
+                               (int)form, G.data_ptr<float>(), p2.data_ptr<float>(), as_dgs(cur_stream())),
+          "pair_probe");
+    return std::make_tuple(G, p2);
+}
+
 // PreprocessCUDA (sample_points.h:20-27)
 PreOut PreprocessCUDA(const Tensor &means, const Tensor &values, const Tensor &covariances,
                       const Tensor &conics, const Tensor &samples, const bool debug) {
@@ -1078,6 +1120,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("preprocess_gaussians_capturable", &PreprocessCapturableCUDA);
     m.def("radix_sort_test", &RadixSortTest);
     m.def("debug_fc_prof", &DebugFcProf);
+    m.def("preprocess_gaussians_refcut", &PreprocessRefCutCUDA);
+    m.def("exp2_probe", &Exp2Probe);
+    m.def("pair_probe", &PairProbe);
+    m.def("qcut_fast", []() { return dgs_debug_qcut_fast(); });
+    m.def("cut_constants", []() {  // (kQCut, kQCutFast, kRho2Max, kExp2FlushBelow)
+        double c[4];
+        dgs_debug_cut_constants(c);
+        return std::make_tuple(c[0], c[1], c[2], c[3]);
+    });
     m.def("volume_preprocess", &VolumePreprocess);
     m.def("volume_forward", &VolumeForward);
     m.def("volume_backward", &VolumeBackward);

@@ -99,7 +99,7 @@ int dgs_preprocess(int P, int D, int N, const float *means, const float *covaria
  * struct_size and flags; dgs_binning_info writes 6 values.  12: dgs_bin_options.samples_binned,
  * dgs_preprocess_auto_ex, dgs_sample_reuse_count.  (dgs_sample_grad_workspace_size and
  * dgs_sample_backward_samples were added at 12 too: new exported functions change no existing
- * layout or signature, so the number stays.) */
+ * layout or signature, so the number stays.  So does DGS_BIN_QCUT_REFERENCE, a new flag bit.) */
 #define DGS_ABI_VERSION 12
 
 /* dgs_bin_options.flags */
@@ -113,7 +113,14 @@ enum {
      * fixed collocation points), and keeps that buffer allocated as long as the graph.  The
      * captured binning then copies the sample side instead of sorting the samples at every replay,
      * and status bit 8 (the samples' own grid) is not computed. */
-    DGS_BIN_SAMPLES_FIXED = 2
+    DGS_BIN_SAMPLES_FIXED = 2,
+    /* diagnostics (from bit 8 up; also accepted by dgs_preprocess_auto_ex).  The reference cut
+     * X^T A X <= 210 for every list entry, instead of the tighter cut of entries only the fast
+     * paths evaluate (whose v_exp_f32 already returns +0 beyond X^T A X = 176): the lists of the
+     * releases before that cut, for A/B timing and for the equivalence tests.  Results agree up to
+     * float summation order.  The environment variable DGS_QCUT_REFERENCE=1 (read once) sets it
+     * for every binning of the process. */
+    DGS_BIN_QCUT_REFERENCE = 0x100
 };
 
 /* Options of dgs_preprocess_ex (zero-initialise, set struct_size = sizeof(dgs_bin_options), then
@@ -121,7 +128,7 @@ enum {
  * refused with DGS_ERR_ARG). */
 typedef struct dgs_bin_options {
     uint32_t struct_size;
-    uint32_t flags; /* DGS_BIN_STATUS_STICKY, DGS_BIN_SAMPLES_FIXED */
+    uint32_t flags; /* DGS_BIN_STATUS_STICKY, DGS_BIN_SAMPLES_FIXED, DGS_BIN_QCUT_REFERENCE */
     /* device uint8[P] or NULL.  Gaussians with present[g] == 0 are left out of the binning the
      * way a det == 0 Gaussian is (radius 0, no tiles, no pairs; radii[g] = 0 and they do not
      * count in num_rendered).  A rank of a spatially sharded run bins only the rows it holds
