@@ -1626,7 +1626,8 @@ __host__ __device__ constexpr bool bwd_mfma() {
 
 // One 16-sample step's operands of lane (q, col): samples s0 + 4q + i (position; dl[.][col], the
 // second product's A) and sample s0 + col (dl[.][4q + j], the first product's A).  Rows past the
-// cell are the next cell's, or k_pack_samples' zero rows past N: finite, and their G is 0.
+// cell are the next cell's, or k_pack_samples' zero rows past N: only a cell's last step holds
+// them, and bwd_mx_pass selects their operands to 0 there (their dL may be non-finite).
 struct MxStep {
     float2 xy[4];
     float a2[4];
@@ -1704,17 +1705,32 @@ __device__ __forceinline__ void bwd_mx_pass(const Bins &bins, const float *__res
         ps += 16 * RSS;
         pc += 16 * RSS;
         if (base + 16 < se) mx_load<D>(ps, pc, col, RSS, nxt);  // (the next step's rows in flight)
-        const float a1[4] = {cur.a1[0].x, cur.a1[0].y, cur.a1[1].x, cur.a1[1].y};
+        float a1[4] = {cur.a1[0].x, cur.a1[0].y, cur.a1[1].x, cur.a1[1].y};
+        bool ok[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ok[i] = base + 4 * q + i < se;
+        // The cell's last step (wave-uniform) may hold rows at or past se: another cell's samples,
+        // which the reference never pairs with these Gaussians.  They contribute selected zeros,
+        // not products with G = 0: their dL may be inf / NaN, or overflow in the contraction.
+        const bool last = base + 16 > se;
+        if (last) {
+            const bool own = base + col < se;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a1[j] = own ? a1[j] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cur.a2[i] = ok[i] ? cur.a2[i] : 0.0f;
+        }
         f32x4_t dg[NG];  // dL/dG of (sample base + 4q + i, Gaussian col of group g)
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             dg[g] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int j = 0; j < 4; ++j) dg[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j], bv[g][j], dg[g], 0, 0, 0);
-        }
-        bool ok[4];
+            if (last) {  // (0 x a non-finite value of Gaussian col: t = G dL/dG below is then 0 x 0)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ok[i] = base + 4 * q + i < se;
+                for (int i = 0; i < 4; ++i) dg[g][i] = ok[i] ? dg[g][i] : 0.0f;
+            }
+        }
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             float G[4];

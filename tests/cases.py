@@ -150,14 +150,14 @@ def clustered_case(P=4000, n=30000, C=1, seed=161):
     return means, values, covs, conics, samples
 
 
-def mixed_scales_case(P=3000, n=25000, C=1, seed=171):
-    """Scales from 1e-4 to 0.2 (log-uniform) with axis ratios up to 5 and random rotations: tiny
-    Gaussians under the radius floor, culled ones, and unculled ones whose cut exceeds half the
-    period (full-tile lists) in one problem; one sample in eight duplicated 4 times (zero-width
-    sub-cell boxes)."""
+def mixed_scales_case(P=3000, n=25000, C=1, seed=171, decades=(-4.0, 2.7)):
+    """Scales from 1e-4 to 0.2 (log-uniform; sigma_min = 10^(decades[0] + decades[1] u)) with axis
+    ratios up to 5 and random rotations: tiny Gaussians under the radius floor, culled ones, and
+    unculled ones whose cut exceeds half the period (full-tile lists) in one problem; one sample
+    in eight duplicated 4 times (zero-width sub-cell boxes)."""
     g = torch.Generator().manual_seed(seed)
     means = torch.rand(P, 2, generator=g, dtype=torch.float64) * 2 - 1
-    s_min = 10 ** (-4 + 2.7 * torch.rand(P, generator=g, dtype=torch.float64))
+    s_min = 10 ** (decades[0] + decades[1] * torch.rand(P, generator=g, dtype=torch.float64))
     s_max = s_min * (1 + 4 * torch.rand(P, generator=g, dtype=torch.float64))
     th = torch.rand(P, generator=g, dtype=torch.float64) * math.pi
     c, sn = torch.cos(th), torch.sin(th)
