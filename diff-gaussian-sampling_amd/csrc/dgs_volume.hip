@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "dgs.h"
 #include "dgs_internal.h"
@@ -697,12 +698,11 @@ __host__ __device__ constexpr float vol_inv_mult(int u) {
     return 1.0f;
 }
 
+// phi, g = d phi / d a and e = d phi / d c (packed) of one function from the sample's tensor H.
+// Entries a function does not have (g of the gaussian, e below the laplacian) are left as given.
 template <int FN>
-__device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const float *c2, const float *s,
-                                           const float *H, VMom &M) {
-    float X[3], a[3], G;
-    if (!pair_eval(m, s, c, X, G, a)) return;
-    float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+__device__ __forceinline__ void phi_ge_t(const float *H, const float *a, const float *c2, float &phi, float *g,
+                                         float *e) {
     if constexpr (FN == 0) {
         phi = H[0];
     } else if constexpr (FN == 1) {
@@ -737,6 +737,12 @@ __device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const
         g[0] = 3.0f * (w0 - M0); g[1] = 3.0f * (w1 - M1); g[2] = 3.0f * (w2 - M2);
         e[0] = 3.0f * E00; e[1] = 6.0f * E01; e[2] = 6.0f * E02; e[3] = 3.0f * E11; e[4] = 6.0f * E12; e[5] = 3.0f * E22;
     }
+}
+
+// Adds one pair's moments for phi, g, e of function order up to TOP (g from 1, e from 2).
+template <int TOP>
+__device__ __forceinline__ void vol_mom_add(float G, float phi, const float *g, const float *e, const float *X,
+                                            VMom &M) {
     const float Gp = G * phi;
     M.sphi += Gp;
     const float XX[6] = {X[0] * X[0], X[0] * X[1], X[0] * X[2], X[1] * X[1], X[1] * X[2], X[2] * X[2]};
@@ -744,7 +750,7 @@ __device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const
     for (int d = 0; d < 3; ++d) M.spx[d] += Gp * X[d];
 #pragma unroll
     for (int q = 0; q < 6; ++q) M.spxx[q] += Gp * XX[q];
-    if constexpr (FN >= 1) {
+    if constexpr (TOP >= 1) {
         const float Gg[3] = {G * g[0], G * g[1], G * g[2]};
 #pragma unroll
         for (int d = 0; d < 3; ++d) M.sg[d] += Gg[d];
@@ -755,10 +761,20 @@ __device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const
         M.sgx[4] += Gg[1] * X[2] + Gg[2] * X[1];
         M.sgx[5] += Gg[2] * X[2];
     }
-    if constexpr (FN >= 2) {
+    if constexpr (TOP >= 2) {
 #pragma unroll
         for (int q = 0; q < 6; ++q) M.se[q] += G * e[q];
     }
+}
+
+template <int FN>
+__device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const float *c2, const float *s,
+                                           const float *H, VMom &M) {
+    float X[3], a[3], G;
+    if (!pair_eval(m, s, c, X, G, a)) return;
+    float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    phi_ge_t<FN>(H, a, c2, phi, g, e);
+    vol_mom_add<FN>(G, phi, g, e, X, M);
 }
 
 __device__ __forceinline__ void vol_mom_finish(const float *c, const VMom &M, float *dm, float *dc, float *dv) {
@@ -963,6 +979,432 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
         __syncthreads();
     }
 }
+
+// ------------------------------------------------------------------------------ fused functions
+// Several of the four functions of one field at the same samples (C = 1; DESIGN.md 4.8, "fused
+// functions"): one walk of the candidates, one pair_eval per kept pair, for every function of
+// MASK (bit f = function f).  The walks are those of k_vol_forward<FN, 1> / k_vol_backward<FN, 1>.
+__host__ __device__ constexpr int mask_ku(int mask) {
+    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0);
+}
+// offset of function f's unique components in a concatenated row of the mask's functions
+__host__ __device__ constexpr int mask_off(int mask, int f) { return mask_ku(mask & ((1 << f) - 1)); }
+__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & 4 ? 2 : mask & 2 ? 1 : 0; }
+
+struct VOuts {
+    float *p[4];  // per function code; entries outside the mask unused
+};
+
+// acc[u] += v G t_u for function FN with the roundings k_vol_forward<FN, 1> has as compiled, written
+// out so that a fused output equals the single call's bit for bit: among the staged candidates
+// the sum is fma(v, G, acc) for the gaussian and fma(round(v G), t_u, acc) for the others; among
+// the big Gaussians (BIG) the product is loop-invariant there, so it is rounded on its own and
+// then added ("fused functions").
+template <int FN, bool BIG>
+__device__ __forceinline__ void fwd_acc(float v, float G, const float *a, const float *c, float *acc) {
+    constexpr int KU = VTr<FN>::KU;
+    float t[KU];
+    terms<FN>(a, c, t);
+    if constexpr (BIG) {
+        const float vG = rmul(v, G);
+        for (int u = 0; u < KU; ++u) acc[u] = radd(acc[u], rmul(vG, t[u]));
+    } else if constexpr (FN == 0) {
+        acc[0] = __builtin_fmaf(v, G, acc[0]);
+    } else {
+        const float vG = rmul(v, G);
+        for (int u = 0; u < KU; ++u) acc[u] = __builtin_fmaf(vG, t[u], acc[u]);
+    }
+}
+template <int FN>
+__device__ __forceinline__ void fwd_store(float *__restrict__ out, int64_t sid, const float *acc) {
+    constexpr int K = VTr<FN>::K;
+    for (int f = 0; f < K; ++f) out[sid * K + f] = acc[umap<FN>(f)];
+}
+template <int FN>
+__device__ __forceinline__ void fwd_nan(float *__restrict__ out, int64_t sid) {
+    constexpr int K = VTr<FN>::K;
+    for (int f = 0; f < K; ++f) out[sid * K + f] = NAN;
+}
+
+template <int MASK>
+__global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict__ buf, int P, int N,
+                                                         const float *__restrict__ means,
+                                                         const float *__restrict__ values,
+                                                         const float *__restrict__ conics,
+                                                         const float *__restrict__ samples, VOuts outs) {
+    constexpr int SKU = mask_ku(MASK);
+    constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    __shared__ VCand<1> cand[kWave];
+    const Hdr &h = hdr_of(buf);  // read in place: a local copy indexed by the axis would live in scratch
+    const int lane = threadIdx.x;
+    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+        for (int64_t j = (int64_t)blockIdx.x * kWave + lane; j < N; j += (int64_t)gridDim.x * kWave) {
+            if constexpr ((MASK & 1) != 0) fwd_nan<0>(outs.p[0], j);
+            if constexpr ((MASK & 2) != 0) fwd_nan<1>(outs.p[1], j);
+            if constexpr ((MASK & 4) != 0) fwd_nan<2>(outs.p[2], j);
+            if constexpr ((MASK & 8) != 0) fwd_nan<3>(outs.p[3], j);
+        }
+        return;
+    }
+    const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
+    const int32_t *__restrict__ sids = reinterpret_cast<const int32_t *>(buf + h.o_sids);
+    const int32_t *__restrict__ gstart = reinterpret_cast<const int32_t *>(buf + h.o_gstart);
+    const int32_t *__restrict__ sstart = reinterpret_cast<const int32_t *>(buf + h.o_sstart);
+    const float4 *__restrict__ gpk = reinterpret_cast<const float4 *>(buf + h.o_gpk);
+    const float4 *__restrict__ gek = reinterpret_cast<const float4 *>(buf + h.o_gek);
+
+    for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
+        const int sb = sstart[cell], se = sstart[cell + 1];
+        const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
+        for (int j0 = sb; j0 < se; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool active = j < se;
+            const int sid = active ? sids[j] : 0;
+            float s[3];
+            for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
+            float acc[SKU];
+            for (int u = 0; u < SKU; ++u) acc[u] = 0.0f;
+            auto eval = [&](const float *m, const float *c, float v, auto big) {
+                constexpr bool BIG = decltype(big)::value;
+                float X[3], a[3], G;
+                if (!pair_eval(m, s, c, X, G, a)) return;
+                if constexpr ((MASK & 1) != 0) fwd_acc<0, BIG>(v, G, a, c, acc + O0);
+                if constexpr ((MASK & 2) != 0) fwd_acc<1, BIG>(v, G, a, c, acc + O1);
+                if constexpr ((MASK & 4) != 0) fwd_acc<2, BIG>(v, G, a, c, acc + O2);
+                if constexpr ((MASK & 8) != 0) fwd_acc<3, BIG>(v, G, a, c, acc + O3);
+            };
+            if (h.nsmall > 0) {
+                // the chunk's sample box (its cell's, widened by the rounding of the grid)
+                float bl[3], bh[3];
+                Win w[3];
+                for (int d = 0; d < 3; ++d) {
+                    bl[d] = h.lo[d] + h.cs[d] * cc[d] - 1e-5f;
+                    bh[d] = h.lo[d] + h.cs[d] * (cc[d] + 1) + 1e-5f;
+                    if (cc[d] == 0) bl[d] = -INFINITY;  // (clamped cells hold everything below / above)
+                    if (cc[d] == h.n[d] - 1) bh[d] = INFINITY;
+                    float mn = INFINITY, mx = -INFINITY;
+                    if (active) { mn = s[d]; mx = s[d]; }
+                    for (int o = kWave / 2; o > 0; o >>= 1) {
+                        mn = fminf(mn, __shfl_xor(mn, o));
+                        mx = fmaxf(mx, __shfl_xor(mx, o));
+                    }
+                    bl[d] = fmaxf(bl[d], mn);
+                    bh[d] = fminf(bh[d], mx);
+                    const float ghi = h.lo[d] + h.cs[d] * h.n[d];
+                    const Win wa = image_range(bl[d], h.E[d], h.lo[d], ghi, true);
+                    const Win wb = image_range(bh[d], h.E[d], h.lo[d], ghi, true);
+                    w[d].k0 = min(wa.k0, wb.k0);
+                    w[d].k1 = max(wa.k1, wb.k1);
+                }
+                for (int cls = 0; cls < 2; ++cls)  // per class: its own reach
+                for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
+                    for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
+                        for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
+                            const int kk[3] = {kx, ky, kz};
+                            int c0[3], c1[3];
+                            bool any = true;
+                            for (int d = 0; d < 3; ++d) {
+                                float xa, xb;
+                                image_window(kk[d], h.Ec[cls][d], xa, xb);
+                                const float ta = bl[d] + xa, tb = bh[d] + xb;  // mean window
+                                const float glo = h.lo[d], ghi = h.lo[d] + h.cs[d] * h.n[d];
+                                if (tb < glo || ta > ghi) { any = false; break; }
+                                c0[d] = cell_axis(h, d, ta);
+                                c1[d] = cell_axis(h, d, tb);
+                            }
+                            if (!any) continue;
+                            for (int cz = c0[2]; cz <= c1[2]; ++cz)
+                                for (int cy = c0[1]; cy <= c1[1]; ++cy) {
+                                    const int row = cls * h.ncells + (cz * h.n[1] + cy) * h.n[0];
+                                    const int b = gstart[row + c0[0]], e = gstart[row + c1[0] + 1];
+                                    for (int q0 = b; q0 < e; q0 += kWave) {
+                                        const int q = q0 + lane;
+                                        __syncthreads();
+                                        if (q < e) {
+                                            VCand<1> v;
+                                            v.mp = gpk[q];
+                                            v.ge = gek[q];
+                                            const int g = __float_as_int(v.mp.w);
+                                            for (int k = 0; k < 6; ++k) v.c[k] = conics[(int64_t)g * 6 + k];
+                                            v.v[0] = values[g];
+                                            cand[lane] = v;
+                                        }
+                                        __syncthreads();
+                                        const int cnt = min(kWave, e - q0);
+                                        if (active)
+                                            for (int u = 0; u < cnt; ++u) {
+                                                const float4 mp = cand[u].mp, ge = cand[u].ge;
+                                                const float m[3] = {mp.x, mp.y, mp.z};
+                                                const float r[3] = {ge.x, ge.y, ge.z};
+                                                bool mine = true;
+                                                for (int d = 0; d < 3; ++d) {  // inside its cut box at image kk
+                                                    const float x = m[d] - s[d];
+                                                    mine = mine && fabsf(x - 2.0f * kk[d]) <= r[d] + 1e-5f;
+                                                }
+                                                if (mine) eval(m, cand[u].c, cand[u].v[0], std::false_type{});
+                                            }
+                                    }
+                                }
+                        }
+            }
+            if (active) {
+                for (int q = gstart[2 * h.ncells]; q < gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = gids[q];
+                    float m[3], c[6];
+                    for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+                    for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                    eval(m, c, values[g], std::true_type{});
+                }
+                if constexpr ((MASK & 1) != 0) fwd_store<0>(outs.p[0], sid, acc + O0);
+                if constexpr ((MASK & 2) != 0) fwd_store<1>(outs.p[1], sid, acc + O1);
+                if constexpr ((MASK & 4) != 0) fwd_store<2>(outs.p[2], sid, acc + O2);
+                if constexpr ((MASK & 8) != 0) fwd_store<3>(outs.p[3], sid, acc + O3);
+            }
+        }
+    }
+}
+
+// k_vol_hsum at C = 1 into function FN's slice of the concatenated rows hs[N][stride]
+template <int FN>
+__global__ __launch_bounds__(kBlock) void k_vol_hsum_cat(int N, const float *__restrict__ dL, float *__restrict__ hs,
+                                                         int stride, int off) {
+    constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    const int64_t sid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (sid >= N) return;
+    float h[KU];
+    for (int u = 0; u < KU; ++u) h[u] = 0.0f;
+#pragma unroll
+    for (int f = 0; f < K; ++f) h[umap<FN>(f)] += dL[sid * K + f];
+    for (int u = 0; u < KU; ++u) hs[sid * stride + off + u] = h[u];
+}
+
+// function FN's slice of a staged row: the tensor H of phi_ge_t
+template <int FN>
+__device__ __forceinline__ void stage_h(float *row, const float *__restrict__ hrow) {
+    for (int u = 0; u < VTr<FN>::KU; ++u) row[u] = hrow[u] * vol_inv_mult<FN>(u);
+}
+// phi, g and e of function FN added to the pair's sums
+template <int FN>
+__device__ __forceinline__ void phi_ge_add(const float *H, const float *a, const float *c2, float &phi, float *g,
+                                           float *e) {
+    float p, gf[3] = {0.0f, 0.0f, 0.0f}, ef[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    phi_ge_t<FN>(H, a, c2, p, gf, ef);
+    phi += p;
+    if constexpr (FN >= 1)
+        for (int d = 0; d < 3; ++d) g[d] += gf[d];
+    if constexpr (FN >= 2)
+        for (int q = 0; q < 6; ++q) e[q] += ef[q];
+}
+
+template <int MASK>
+__global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict__ buf, int P, int N,
+                                                          const float *__restrict__ means,
+                                                          const float *__restrict__ values,
+                                                          const float *__restrict__ conics,
+                                                          const float *__restrict__ samples,
+                                                          const float *__restrict__ hs, float *__restrict__ dmeans,
+                                                          float *__restrict__ dvalues, float *__restrict__ dconics) {
+    constexpr int SKU = mask_ku(MASK), TOP = mask_top(MASK);
+    constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    __shared__ float4 scand[kWave];
+    __shared__ float shrow[kWave][SKU];  // the candidates' H rows, function after function
+    const Hdr &h = hdr_of(buf);  // (in place, as k_vol_forward_m)
+    const int lane = threadIdx.x;
+    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+        const float nan[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+        for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < P; i += (int64_t)gridDim.x * kWave)
+            bwd_store<1>((int)i, 1, 0, 1, nan, nan, nan, dmeans, dvalues, dconics);
+        return;
+    }
+    const int32_t *__restrict__ sids = reinterpret_cast<const int32_t *>(buf + h.o_sids);
+    const int32_t *__restrict__ gstart = reinterpret_cast<const int32_t *>(buf + h.o_gstart);
+    const int32_t *__restrict__ sstart = reinterpret_cast<const int32_t *>(buf + h.o_sstart);
+    const float4 *__restrict__ gpk = reinterpret_cast<const float4 *>(buf + h.o_gpk);
+    const float4 *__restrict__ gek = reinterpret_cast<const float4 *>(buf + h.o_gek);
+    for (int cell = blockIdx.x; cell < 2 * h.ncells; cell += gridDim.x) {  // (class-major cells)
+        const int gb = gstart[cell], ge = gstart[cell + 1];
+        for (int i0 = gb; i0 < ge; i0 += kWave) {
+            const int i = i0 + lane;
+            const bool active = i < ge;
+            float m[3] = {0.0f, 0.0f, 0.0f}, r[3] = {0.0f, 0.0f, 0.0f}, c[6];
+            int g = 0;
+            float v0 = 0.0f;
+            if (active) {
+                const float4 mp = gpk[i], ex = gek[i];
+                g = __float_as_int(mp.w);
+                v0 = values[g];
+                m[0] = mp.x; m[1] = mp.y; m[2] = mp.z;
+                r[0] = ex.x; r[1] = ex.y; r[2] = ex.z;
+                for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+            } else {
+                for (int k = 0; k < 6; ++k) c[k] = 0.0f;
+            }
+            VMom mom{};
+            const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
+            float ml[3], mh[3], R[3];
+            Win w[3];
+            for (int d = 0; d < 3; ++d) {
+                float mn = active ? m[d] : INFINITY, mx = active ? m[d] : -INFINITY, rr = r[d];
+                for (int o = kWave / 2; o > 0; o >>= 1) {
+                    mn = fminf(mn, __shfl_xor(mn, o));
+                    mx = fmaxf(mx, __shfl_xor(mx, o));
+                    rr = fmaxf(rr, __shfl_xor(rr, o));
+                }
+                ml[d] = mn; mh[d] = mx; R[d] = rr;
+                const float ghi = h.lo[d] + h.cs[d] * h.n[d];
+                const Win wa = image_range(mn, rr, h.lo[d], ghi, false);
+                const Win wb = image_range(mx, rr, h.lo[d], ghi, false);
+                w[d].k0 = min(wa.k0, wb.k0);
+                w[d].k1 = max(wa.k1, wb.k1);
+            }
+            for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
+                for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
+                    for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
+                        const int kk[3] = {kx, ky, kz};
+                        int c0[3], c1[3];
+                        bool any = true;
+                        for (int d = 0; d < 3; ++d) {
+                            float xa, xb;
+                            image_window(kk[d], R[d], xa, xb);
+                            const float ta = ml[d] - xb, tb = mh[d] - xa;  // sample window
+                            const float glo = h.lo[d], ghi = h.lo[d] + h.cs[d] * h.n[d];
+                            if (tb < glo || ta > ghi) { any = false; break; }
+                            c0[d] = cell_axis(h, d, ta);
+                            c1[d] = cell_axis(h, d, tb);
+                        }
+                        if (!any) continue;
+                        for (int cz = c0[2]; cz <= c1[2]; ++cz)
+                            for (int cy = c0[1]; cy <= c1[1]; ++cy) {
+                                const int row = (cz * h.n[1] + cy) * h.n[0];
+                                const int b = sstart[row + c0[0]], e = sstart[row + c1[0] + 1];
+                                for (int q0 = b; q0 < e; q0 += kWave) {
+                                    const int q = q0 + lane;
+                                    __syncthreads();
+                                    if (q < e) {
+                                        const int sid = sids[q];
+                                        scand[lane] = make_float4(samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1],
+                                                                  samples[(int64_t)sid * 3 + 2], __int_as_float(sid));
+                                        const float *__restrict__ hrow = hs + (int64_t)sid * SKU;
+                                        if constexpr ((MASK & 1) != 0) stage_h<0>(&shrow[lane][O0], hrow + O0);
+                                        if constexpr ((MASK & 2) != 0) stage_h<1>(&shrow[lane][O1], hrow + O1);
+                                        if constexpr ((MASK & 4) != 0) stage_h<2>(&shrow[lane][O2], hrow + O2);
+                                        if constexpr ((MASK & 8) != 0) stage_h<3>(&shrow[lane][O3], hrow + O3);
+                                    }
+                                    __syncthreads();
+                                    const int cnt = min(kWave, e - q0);
+                                    if (active)
+                                        for (int u = 0; u < cnt; ++u) {
+                                            const float4 sp = scand[u];
+                                            const float sv[3] = {sp.x, sp.y, sp.z};
+                                            bool mine = true;
+                                            for (int d = 0; d < 3; ++d) {  // inside its cut box at image kk
+                                                const float x = m[d] - sv[d];
+                                                mine = mine && fabsf(x - 2.0f * kk[d]) <= r[d] + 1e-5f;
+                                            }
+                                            if (!mine) continue;
+                                            float X[3], a[3], G;
+                                            if (!pair_eval(m, sv, c, X, G, a)) continue;
+                                            const float *H = &shrow[u][0];
+                                            float phi = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f};
+                                            float ee[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                                            if constexpr ((MASK & 1) != 0) phi_ge_add<0>(H + O0, a, c2, phi, gg, ee);
+                                            if constexpr ((MASK & 2) != 0) phi_ge_add<1>(H + O1, a, c2, phi, gg, ee);
+                                            if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, gg, ee);
+                                            if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, gg, ee);
+                                            vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
+                                        }
+                                }
+                            }
+                    }
+            float dm[3], dc[6], dv[1];
+            vol_mom_finish(c, mom, dm, dc, dv);
+            if (active) bwd_store<1>(g, 1, 0, 1, dm, dc, dv, dmeans, dvalues, dconics, v0);
+        }
+    }
+}
+
+// Big Gaussians of the fused backward: the per-function pair terms into the same sums, rows
+// written once.
+template <int MASK>
+__global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__restrict__ buf, int P, int N,
+                                                               const float *__restrict__ means,
+                                                               const float *__restrict__ values,
+                                                               const float *__restrict__ conics,
+                                                               const float *__restrict__ samples,
+                                                               const float *__restrict__ hs,
+                                                               float *__restrict__ dmeans,
+                                                               float *__restrict__ dvalues,
+                                                               float *__restrict__ dconics) {
+    constexpr int NV = 10, SKU = mask_ku(MASK);
+    __shared__ float part[kWavesPerBlock][NV];
+    const Hdr h = hdr_of(buf);
+    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) return;  // (k_vol_backward_m flags it)
+    const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    for (int b = blockIdx.x; b < h.nbig; b += gridDim.x) {
+        const int g = gids[h.nsmall + b];
+        float m[3], c[6];
+        for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+        for (int q = 0; q < 6; ++q) c[q] = conics[(int64_t)g * 6 + q];
+        const float v0 = values[g];
+        float v[NV];
+        for (int k = 0; k < NV; ++k) v[k] = 0.0f;
+        for (int sid = threadIdx.x; sid < N; sid += kBlock) {
+            const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
+            const float *hrow = hs + (int64_t)sid * SKU;
+            if constexpr ((MASK & 1) != 0)
+                bwd_pair<0, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 0), v, v + 3, v + 9);
+            if constexpr ((MASK & 2) != 0)
+                bwd_pair<1, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 1), v, v + 3, v + 9);
+            if constexpr ((MASK & 4) != 0)
+                bwd_pair<2, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
+            if constexpr ((MASK & 8) != 0)
+                bwd_pair<3, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
+        }
+        for (int k = 0; k < NV; ++k)
+            for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+        if (lane == 0)
+            for (int k = 0; k < NV; ++k) part[w][k] = v[k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t[NV];
+            for (int k = 0; k < NV; ++k) {
+                t[k] = 0.0f;
+                for (int q = 0; q < kWavesPerBlock; ++q) t[k] += part[q][k];
+            }
+            bwd_store<1>(g, 1, 0, 1, t, t + 3, t + 9, dmeans, dvalues, dconics, v0);
+        }
+        __syncthreads();
+    }
+}
+
+template <int MASK>
+static void launch_fwd_m(const char *buf, int P, int N, const float *means, const float *values,
+                         const float *conics, const float *samples, float *const *outs, hipStream_t s) {
+    VOuts o;
+    for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? outs[f] : nullptr;
+    k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, s>>>(buf, P, N, means, values, conics, samples, o);
+}
+template <int FN>
+static void launch_hsum_cat(int mask, int N, const float *const *dLs, float *hs, hipStream_t s) {
+    if (!((mask >> FN) & 1)) return;
+    k_vol_hsum_cat<FN><<<(unsigned)((N + kBlock - 1) / kBlock), kBlock, 0, s>>>(N, dLs[FN], hs, mask_ku(mask),
+                                                                                 mask_off(mask, FN));
+}
+template <int MASK>
+static void launch_bwd_m(const char *buf, int P, int N, const float *means, const float *values,
+                         const float *conics, const float *samples, const float *const *dLs, float *hs, float *dm,
+                         float *dv, float *dc, hipStream_t s) {
+    launch_hsum_cat<0>(MASK, N, dLs, hs, s);
+    launch_hsum_cat<1>(MASK, N, dLs, hs, s);
+    launch_hsum_cat<2>(MASK, N, dLs, hs, s);
+    launch_hsum_cat<3>(MASK, N, dLs, hs, s);
+    k_vol_backward_m<MASK><<<kVolBwdBlocks, kWave, 0, s>>>(buf, P, N, means, values, conics, samples, hs, dm, dv, dc);
+    k_vol_backward_big_m<MASK><<<256, kBlock, 0, s>>>(buf, P, N, means, values, conics, samples, hs, dm, dv, dc);
+}
+
+// the 11 masks of two or more functions
+#define DGS_VOL_MASKS(X) X(3) X(5) X(6) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 
 static int vol_cb(int C) { return C <= 1 ? 1 : C <= 4 ? 4 : 8; }
 
@@ -1200,6 +1642,90 @@ extern "C" int dgs_volume_backward(int function, int P, int N, int C, const floa
         case 1: dispatch_bwd<1>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
         case 2: dispatch_bwd<2>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
         default: dispatch_bwd<3>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+// ---- fused functions (include/dgs_volume.h) ----
+static int vol_mask_single(int mask) {  // the function of a single-bit mask, else -1
+    return mask == 1 ? 0 : mask == 2 ? 1 : mask == 4 ? 2 : mask == 8 ? 3 : -1;
+}
+
+static int vol_check_multi(int mask, int P, int N, int C, const void *binning, size_t bytes) {
+    if (mask < 1 || mask > 15) return fail(DGS_ERR_ARG, "dgs_volume_*_multi: mask must be 1..15");
+    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
+    if (vol_mask_single(mask) < 0 && C != 1)
+        return fail(DGS_ERR_ARG,
+                    "dgs_volume_*_multi: several functions need C = 1; call the per-function entry points and add");
+    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+    return DGS_OK;
+}
+
+extern "C" size_t dgs_volume_workspace_size_multi(int mask, int P, int N, int C, int backward) {
+    if (mask < 1 || mask > 15) return 0;
+    const int f = vol_mask_single(mask);
+    if (f >= 0) return dgs_volume_workspace_size(f, P, N, C, backward);
+    if (!backward || N <= 0 || C != 1) return 0;
+    return (size_t)N * mask_ku(mask) * 4;
+}
+
+extern "C" int dgs_volume_forward_multi(int mask, int P, int N, int C, const float *means, const float *values,
+                                        const float *conics, const float *samples, const void *binning,
+                                        size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug) {
+    if (int rc = vol_check_multi(mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_multi: outs required");
+    const int f = vol_mask_single(mask);
+    if (f >= 0)
+        return dgs_volume_forward(f, P, N, C, means, values, conics, samples, binning, binning_bytes, outs[f], stream,
+                                  debug);
+    if (N == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const char *buf = static_cast<const char *>(binning);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
+    switch (mask) {
+#define X(M) case M: launch_fwd_m<M>(buf, P, N, means, values, conics, samples, outs, s); break;
+        DGS_VOL_MASKS(X)
+#undef X
+        default: return fail(DGS_ERR_ARG, "dgs_volume_forward_multi: mask");
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_multi(int mask, int P, int N, int C, const float *means, const float *values,
+                                         const float *conics, const float *samples, const float *const *dL_douts,
+                                         const void *binning, size_t binning_bytes, float *dL_dmeans,
+                                         float *dL_dvalues, float *dL_dconics, void *workspace,
+                                         size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    if (int rc = vol_check_multi(mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: dL_douts required");
+    const int f = vol_mask_single(mask);
+    if (f >= 0)
+        return dgs_volume_backward(f, P, N, C, means, values, conics, samples, dL_douts[f], binning, binning_bytes,
+                                   dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
+    if (workspace_bytes < dgs_volume_workspace_size_multi(mask, P, N, C, 1))
+        return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) return DGS_OK;
+    if (N == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * 4, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
+        return DGS_OK;
+    }
+    const char *buf = static_cast<const char *>(binning);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
+    float *hs = static_cast<float *>(workspace);
+    switch (mask) {
+#define X(M)                                                                                                      \
+    case M:                                                                                                       \
+        launch_bwd_m<M>(buf, P, N, means, values, conics, samples, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics, \
+                        s);                                                                                       \
+        break;
+        DGS_VOL_MASKS(X)
+#undef X
+        default: return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: mask");
     }
     DGS_LAUNCH_CHECK(s, debug);
     return DGS_OK;

@@ -1076,6 +1076,86 @@ std::tuple<Tensor, Tensor, Tensor> VolumeBackward(int function, const Tensor &me
     return std::make_tuple(dm, dv, dc);
 }
 
+// Fused functions at D = 3 (dgs_volume_{forward,backward}_multi): `codes` holds distinct codes
+// 0..3; the outputs come back in that order.  Several functions at C = 1 share one walk of the
+// candidates; otherwise (one function, or C > 1, which the C entry refuses) the per-function
+// kernels run in turn and the backward adds their gradients.
+std::vector<Tensor> VolumeForwardMulti(const std::vector<int64_t> &codes, const Tensor &means_in,
+                                       const Tensor &values_in, const Tensor &conics_in, const Tensor &samples_in,
+                                       const Tensor &binning_in, const bool debug) {
+    const int mask = function_mask(codes);
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    std::vector<Tensor> outs;
+    if (codes.size() == 1 || C != 1) {
+        for (int64_t f : codes)
+            outs.push_back(VolumeForward((int)f, means_in, values_in, conics_in, samples_in, binning_in, debug));
+        return outs;
+    }
+    float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int64_t f : codes) {
+        std::vector<int64_t> shape{N};
+        for (int k = 0; k < (int)f; ++k) shape.push_back(3);
+        shape.push_back(C);
+        outs.push_back(torch::zeros(shape, means.options()));
+        ptr[f] = outs.back().data_ptr<float>();
+    }
+    if (N == 0) return outs;
+    check(dgs_volume_forward_multi(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+                                   conics.data_ptr<float>(), samples.data_ptr<float>(), binning.data_ptr(),
+                                   (size_t)binning.numel(), ptr, as_dgs(cur_stream()), debug ? 1 : 0),
+          "volume_forward_multi");
+    return outs;
+}
+
+std::tuple<Tensor, Tensor, Tensor> VolumeBackwardMulti(const std::vector<int64_t> &codes, const Tensor &means_in,
+                                                       const Tensor &values_in, const Tensor &conics_in,
+                                                       const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
+                                                       const Tensor &binning_in, const bool debug) {
+    const int mask = function_mask(codes);
+    TORCH_CHECK(dLs_in.size() == codes.size(), "one dL_dout per sampling function");
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    if (codes.size() == 1 || C != 1) {
+        auto g = VolumeBackward((int)codes[0], means_in, values_in, conics_in, samples_in, binning_in, dLs_in[0], debug);
+        for (size_t i = 1; i < codes.size(); ++i) {
+            auto h = VolumeBackward((int)codes[i], means_in, values_in, conics_in, samples_in, binning_in, dLs_in[i],
+                                    debug);
+            std::get<0>(g).add_(std::get<0>(h));
+            std::get<1>(g).add_(std::get<1>(h));
+            std::get<2>(g).add_(std::get<2>(h));
+        }
+        return g;
+    }
+    std::vector<Tensor> dLs;
+    const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t i = 0; i < codes.size(); ++i) {
+        int64_t K = 1;
+        for (int k = 0; k < (int)codes[i]; ++k) K *= 3;
+        dLs.push_back(f32(dLs_in[i], "dL_dout"));
+        TORCH_CHECK(dLs.back().numel() == N * K * C, "volume: dL_dout must be [N, 3^function, C]");
+        ptr[codes[i]] = dLs.back().data_ptr<float>();
+    }
+    Tensor dm = torch::zeros({P, 3}, means.options()), dv = torch::zeros({P, C}, means.options());
+    Tensor dc = torch::zeros({P, 6}, means.options());
+    if (P == 0) return std::make_tuple(dm, dv, dc);
+    const size_t ws = dgs_volume_workspace_size_multi(mask, (int)P, (int)N, (int)C, 1);
+    Tensor work = torch::empty({(int64_t)std::max<size_t>(ws, 4)}, means.options().dtype(torch::kUInt8));
+    check(dgs_volume_backward_multi(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+                                    conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(),
+                                    (size_t)binning.numel(), dm.data_ptr<float>(), dv.data_ptr<float>(),
+                                    dc.data_ptr<float>(), work.data_ptr(), ws, as_dgs(cur_stream()), debug ? 1 : 0),
+          "volume_backward_multi");
+    return std::make_tuple(dm, dv, dc);
+}
+
 std::tuple<int64_t, int64_t> VolumeCountPairs(const Tensor &means_in, const Tensor &conics_in,
                                               const Tensor &samples_in, const Tensor &binning_in) {
     const Tensor means = f32(means_in, "means"), conics = f32(conics_in, "conics");
@@ -1132,6 +1212,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("volume_preprocess", &VolumePreprocess);
     m.def("volume_forward", &VolumeForward);
     m.def("volume_backward", &VolumeBackward);
+    m.def("volume_forward_multi", &VolumeForwardMulti);
+    m.def("volume_backward_multi", &VolumeBackwardMulti);
     m.def("volume_count_pairs", &VolumeCountPairs);
     m.def("library_version", []() { return dgs_version(); });
     m.def("warmup", []() { check(dgs_warmup(as_dgs(cur_stream())), "warmup"); });

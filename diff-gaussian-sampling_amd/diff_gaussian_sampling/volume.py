@@ -53,6 +53,37 @@ def sample_volume(function, means, values, conics, samples, binning, debug=False
     return _SampleVolume.apply(code, means, values, conics, samples, binning, debug)
 
 
+class _SampleVolumeMulti(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, codes, means, values, conics, samples, binning, debug):
+        if ctx.needs_input_grad[4]:
+            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them")
+        outs = call_debug(_C.volume_forward_multi, debug, "vol_multi_fw", list(codes), means, values, conics,
+                          samples, binning, debug)
+        ctx.codes, ctx.debug = codes, debug
+        ctx.save_for_backward(means, values, conics, samples, binning)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        means, values, conics, samples, binning = ctx.saved_tensors
+        live = [(c, g.contiguous()) for c, g in zip(ctx.codes, grads) if g is not None]
+        if not live:
+            return (None,) * 7
+        gm, gv, gc = call_debug(_C.volume_backward_multi, ctx.debug, "vol_multi_bw", [c for c, _ in live],
+                                means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
+        return None, gm, gv, gc, None, None, None
+
+
+def sample_volume_multi(functions, means, values, conics, samples, binning, debug=False):
+    """Several of the four functions (distinct names or codes) of a D = 3 field at `samples`;
+    returns their outputs in the order asked.  At C = 1 they share one walk of the candidates,
+    forward and backward (include/dgs_volume.h, dgs_volume_*_multi); each output is bitwise the
+    one `sample_volume` returns.  An output whose gradient is None is left out of the backward."""
+    codes = tuple(FUNCTION_CODES[f] if isinstance(f, str) else int(f) for f in functions)
+    return _SampleVolumeMulti.apply(codes, means, values, conics, samples, binning, debug)
+
+
 class VolumeSampler:
     """GaussianSampler's shape for D = 3: preprocess once per (means, conics, samples), then
     sample any of the four functions.  covariances are accepted for signature parity with
@@ -77,7 +108,7 @@ class VolumeSampler:
             return None
         return tuple(t._version for t in ts)
 
-    def _run(self, code):
+    def _rebin_if_changed(self):
         now = self._now()
         # changed in place since the binning (or, for inference tensors, possibly changed: every
         # call after the first re-bins) -> re-bin
@@ -85,8 +116,18 @@ class VolumeSampler:
             self.binning = preprocess_volume(self.means, self.conics, self.samples, self.debug)
             self._versions = self._now()
         self._fresh = False
+
+    def _run(self, code):
+        self._rebin_if_changed()
         return sample_volume(code, self.means, self.values, self.conics, self.samples, self.binning,
                              self.debug)
+
+    def sample_gaussians_multi(self, *functions):
+        """Several functions ("gaussian", "derivative", "laplacian", "third" or 0..3) in one
+        call; returns a tuple in the order asked (sample_volume_multi)."""
+        self._rebin_if_changed()
+        return sample_volume_multi(functions, self.means, self.values, self.conics, self.samples,
+                                   self.binning, self.debug)
 
     def sample_gaussians(self):
         return self._run(0)

@@ -60,6 +60,32 @@ int dgs_volume_backward(int function, int P, int N, int C, const float *means, c
                         float *dL_dvalues, float *dL_dconics, void *workspace,
                         size_t workspace_bytes, dgs_stream_t stream, int debug);
 
+/* Fused functions (the D = 3 form of dgs_sample_*_multi in dgs.h): one walk of the candidates
+ * for every function of `mask` (bit f set = function f, mask in 1..15; DGS_ERR_ARG otherwise),
+ * as a PDE residual needs several of the four at the same points per step.
+ *   forward : outs[f] = out of function f (as dgs_volume_forward, every entry written), for
+ *             every f in mask; the other entries are ignored and may be NULL.  Each output is
+ *             bit-identical to dgs_volume_forward's (the same addends in the same order).
+ *   backward: dL_douts[f] = dL/d out of function f for every f in mask; writes (overwrites)
+ *             the gradients of the summed loss, sum_f <dL_douts[f], out_f>, with no atomics
+ *             (repeated calls are bit-identical).
+ * Two or more functions need C = 1 (DGS_ERR_ARG otherwise: call the per-function entry points
+ * and add their gradients); a single-bit mask is the per-function path for any C, and its
+ * workspace size is dgs_volume_workspace_size's.  Backward workspace of a multi-bit mask:
+ * N * (unique components of the mask's functions: 1 + 3 + 6 + 10 for all four) * 4 bytes; the
+ * forward needs none.  A missing or short binning gives DGS_ERR_BUFFER.  Edge sizes, the stale
+ * buffer / changed input guard (NaN in every output or gradient) and the ordering of calls on
+ * one binning are those of the per-function calls; no host sync, no allocation. */
+size_t dgs_volume_workspace_size_multi(int mask, int P, int N, int C, int backward);
+int dgs_volume_forward_multi(int mask, int P, int N, int C, const float *means, const float *values,
+                             const float *conics, const float *samples, const void *binning,
+                             size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug);
+int dgs_volume_backward_multi(int mask, int P, int N, int C, const float *means, const float *values,
+                              const float *conics, const float *samples, const float *const *dL_douts,
+                              const void *binning, size_t binning_bytes, float *dL_dmeans,
+                              float *dL_dvalues, float *dL_dconics, void *workspace,
+                              size_t workspace_bytes, dgs_stream_t stream, int debug);
+
 /* Diagnostic (not on any reference API): counts[0] = pairs the forward evaluates (candidates
  * inside their own cut box), counts[1] = live pairs (G = expf(power) > 0).  Host, syncs;
  * DGS_ERR_BUFFER when the inputs differ from the binned ones. */

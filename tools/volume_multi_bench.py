@@ -1,0 +1,92 @@
+"""Times the fused D = 3 multi-function call against the per-function calls on one binning.
+
+    python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
+                                       [--rounds 3] [--steps 3] [--separate-only]
+
+The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice, C = 1).  After settle
+steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
+hits both alike; each figure is the median over the rounds of the mean ms per forward +
+backward step (preprocess excluded).  Prints one JSON line: fused_ms, separate_ms (the sum of the
+per-function calls, same outputs and gradients), per-function step times `single_ms`, the speedup,
+and `fused_over_last`, the fused step against the most expensive (last named) function alone.
+--separate-only times the per-function calls only (a package without the fused call, for A/B
+runs through tools/ab.py --script).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.environ.get("DGS_PKG_ROOT", os.path.join(REPO, "diff-gaussian-sampling_amd"))]  # variants: tools/variant.sh
+
+import torch  # noqa: E402
+
+from diff_gaussian_sampling import synthetic as syn  # noqa: E402
+from diff_gaussian_sampling.volume import FUNCTION_CODES, VolumeSampler  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--P", type=int, default=1_000_000)
+    ap.add_argument("--grid3", type=int, default=64)
+    ap.add_argument("--functions", default="gaussian,derivative,laplacian,third")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--settle", type=int, default=2)
+    ap.add_argument("--separate-only", action="store_true")
+    args = ap.parse_args()
+    fns = args.functions.split(",")
+    dev = torch.device("cuda:0")
+    means, values, covs, conics = (t.to(dev) for t in syn.gaussians3(args.P, 1, seed=0))
+    samples = syn.grid_samples3(args.grid3).to(dev)
+    N = samples.shape[0]
+    for t in (means, values, conics):
+        t.requires_grad_(True)
+    vs = VolumeSampler(False)
+    vs.preprocess(means, values, covs, conics, samples)
+    gen = torch.Generator().manual_seed(5)
+    w = {f: torch.randn((N,) + (3,) * FUNCTION_CODES[f] + (1,), generator=gen).to(dev) for f in fns}
+    single = {"gaussian": vs.sample_gaussians, "derivative": vs.sample_gaussians_derivative,
+              "laplacian": vs.sample_gaussians_laplacian, "third": vs.sample_gaussians_third_derivative}
+
+    def step(which):
+        for t in (means, values, conics):
+            t.grad = None
+        if which == "fused":
+            outs = vs.sample_gaussians_multi(*fns)
+            torch.autograd.backward(list(outs), [w[f] for f in fns])
+        else:
+            for f in (fns if which == "separate" else [which]):
+                single[f]().backward(w[f])
+
+    def timed(which):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(which)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+
+    kinds = (["separate"] if args.separate_only else ["fused", "separate"])
+    for k in kinds:
+        for _ in range(args.settle):
+            step(k)
+    times = {k: [] for k in kinds + fns}
+    for _ in range(args.rounds):
+        for k in kinds + fns:
+            times[k].append(timed(k))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    res = {"P": args.P, "N": N, "grid3": args.grid3, "functions": fns, "rounds": args.rounds, "steps": args.steps,
+           "separate_ms": med["separate"], "single_ms": {f: med[f] for f in fns},
+           "separate_rounds_ms": times["separate"]}
+    if not args.separate_only:
+        res.update(fused_ms=med["fused"], fused_rounds_ms=times["fused"], speedup=med["separate"] / med["fused"],
+                   fused_over_last=med["fused"] / med[fns[-1]])
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
