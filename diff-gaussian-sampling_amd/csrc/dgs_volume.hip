@@ -18,7 +18,12 @@
 //   * "big" Gaussians (everything else) sit in one extra cell and meet every sample;
 //   * forward: lane = sample (in cell order), outputs summed in registers, no atomics;
 //     backward: lane = Gaussian (in cell order) walking the samples of its images, gradients
-//     in registers, no atomics; big Gaussians: one block each over every sample.
+//     in registers, no atomics; big Gaussians: one block each over every sample;
+//   * the forward's loop nest is written once (walk_candidates) and called with two callables by
+//     k_vol_forward<FN, CB> at C > 1 and k_vol_forward_m<MASK> at C = 1, where a single function
+//     is the single-bit mask; the backward kernels (k_vol_backward<FN, CB>, k_vol_backward_m<MASK>
+//     for two or more functions) each hold the lane = Gaussian nest: their pair arithmetic is
+//     contracted by the compiler, and its last bits move when the nest does.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -78,12 +83,19 @@ __host__ __device__ constexpr int sort3_idx(int i, int j, int k) {
     return uidx3s(lo, mid, hi);
 }
 
+// Function masks (bit f = function f).  The unique (symmetric) components of a mask's functions:
+// 1, 3, 6 and 10 of the 1, 3, 9 and 27 full ones; every other count derives from this one.
+__host__ __device__ constexpr int mask_ku(int mask) {
+    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0);
+}
+// offset of function f's unique components in a concatenated row of the mask's functions
+__host__ __device__ constexpr int mask_off(int mask, int f) { return mask_ku(mask & ((1 << f) - 1)); }
+__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & 4 ? 2 : mask & 2 ? 1 : 0; }
+
 template <int FN>
-struct VTr;
-template <> struct VTr<0> { static constexpr int KU = 1, K = 1; };
-template <> struct VTr<1> { static constexpr int KU = 3, K = 3; };
-template <> struct VTr<2> { static constexpr int KU = 6, K = 9; };
-template <> struct VTr<3> { static constexpr int KU = 10, K = 27; };
+struct VTr {
+    static constexpr int KU = mask_ku(1 << FN), K = FN == 0 ? 1 : FN == 1 ? 3 : FN == 2 ? 9 : 27;
+};
 
 // unique component of the full output index f (row-major over the 3^FN indices)
 template <int FN>
@@ -415,15 +427,23 @@ __global__ __launch_bounds__(kBlock) void k_vol_pack(int nsmall, const int32_t *
 // the cells and the packed means come from preprocess, so other tensors (an in-place optimizer
 // step, moved samples) would mix old and new parameters.  On a difference the call writes NaN,
 // like a stale buffer (VolumeSampler re-bins before that can happen).
+__device__ __forceinline__ bool hdr_fits(const Hdr &h, int P, int N) {  // a binning of these sizes
+    return h.magic == kVolMagic && h.P == P && h.N == N;
+}
+// the guard of every sampling kernel: a stale buffer, or inputs that differ from the binned ones
+__device__ __forceinline__ bool vol_stale(const char *buf, const Hdr &h, int P, int N) {
+    return !hdr_fits(h, P, N) || *reinterpret_cast<const volatile int *>(buf + h.o_flag) != 0;
+}
+
 __global__ void k_vol_flag_reset(int P, int N, char *buf) {
-    const Hdr h = *reinterpret_cast<const Hdr *>(buf);
-    if (threadIdx.x == 0 && h.magic == kVolMagic && h.P == P && h.N == N) *reinterpret_cast<int *>(buf + h.o_flag) = 0;
+    const Hdr &h = hdr_of(buf);
+    if (threadIdx.x == 0 && hdr_fits(h, P, N)) *reinterpret_cast<int *>(buf + h.o_flag) = 0;
 }
 
 __global__ void k_vol_verify(int P, int N, const uint32_t *__restrict__ m, const uint32_t *__restrict__ c,
                              const uint32_t *__restrict__ sm, char *buf) {
-    const Hdr h = *reinterpret_cast<const Hdr *>(buf);
-    if (h.magic != kVolMagic || h.P != P || h.N != N) return;  // (the kernels flag a stale buffer)
+    const Hdr h = hdr_of(buf);
+    if (!hdr_fits(h, P, N)) return;  // (the kernels flag a stale buffer)
     const int64_t nm = (int64_t)P * 3, nc = (int64_t)P * 6, ns = (int64_t)N * 3;
     const uint32_t *mc = reinterpret_cast<const uint32_t *>(buf + h.o_mcopy);
     const uint32_t *cc = reinterpret_cast<const uint32_t *>(buf + h.o_ccopy);
@@ -437,18 +457,56 @@ __global__ void k_vol_verify(int P, int N, const uint32_t *__restrict__ m, const
 
 // count_pairs: the flag word (or 1 for a stale buffer) into out
 __global__ void k_vol_flag_read(int P, int N, const char *buf, unsigned long long *out) {
-    const Hdr &h = *reinterpret_cast<const Hdr *>(buf);
-    if (threadIdx.x == 0)
-        out[0] = (h.magic != kVolMagic || h.P != P || h.N != N) ? 1ull
-                                                                : (unsigned long long)*reinterpret_cast<const volatile int *>(buf + h.o_flag);
-}
-
-__device__ inline bool vol_flagged(const char *buf, const Hdr &h) {
-    return *reinterpret_cast<const volatile int *>(buf + h.o_flag) != 0;
+    if (threadIdx.x == 0) out[0] = vol_stale(buf, hdr_of(buf), P, N) ? 1ull : 0ull;
 }
 
 __global__ void k_vol_header(Hdr h, char *buf) {
     if (threadIdx.x == 0) *reinterpret_cast<Hdr *>(buf) = h;
+}
+
+// ------------------------------------------------------------------------------ the walks
+// What every sampling kernel starts with: the guard (vol_stale, above) and the binned arrays.  The
+// header is read in place (const Hdr &): a local copy indexed by the axis would live in scratch.
+struct Bin {  // the binned arrays of a buffer
+    const int32_t *__restrict__ gids, *__restrict__ sids, *__restrict__ gstart, *__restrict__ sstart;
+    const float4 *__restrict__ gpk, *__restrict__ gek;
+};
+__device__ __forceinline__ Bin bin_of(const char *buf, const Hdr &h) {
+    return {reinterpret_cast<const int32_t *>(buf + h.o_gids),   reinterpret_cast<const int32_t *>(buf + h.o_sids),
+            reinterpret_cast<const int32_t *>(buf + h.o_gstart), reinterpret_cast<const int32_t *>(buf + h.o_sstart),
+            reinterpret_cast<const float4 *>(buf + h.o_gpk),     reinterpret_cast<const float4 *>(buf + h.o_gek)};
+}
+
+// Images of one axis that a box [pl, ph] of points with reach r can meet inside the grid.
+__device__ __forceinline__ Win box_images(const Hdr &h, int d, float pl, float ph, float r, bool target_is_mean) {
+    const float ghi = h.lo[d] + h.cs[d] * h.n[d];
+    const Win wa = image_range(pl, r, h.lo[d], ghi, target_is_mean);
+    const Win wb = image_range(ph, r, h.lo[d], ghi, target_is_mean);
+    return {min(wa.k0, wb.k0), max(wa.k1, wb.k1)};
+}
+// One axis of a window: the cells [c0, c1] that the targets of the box [pl, ph] under image k and
+// reach r can lie in; false when the window misses the grid.  The windows are in x = m - s, so
+// means lie at p + x of a sample box and samples at p - x of a means box.
+__device__ __forceinline__ bool window_cells(const Hdr &h, int d, int k, float r, float pl, float ph,
+                                             bool target_is_mean, int &c0, int &c1) {
+    float xa, xb;
+    image_window(k, r, xa, xb);
+    const float ta = target_is_mean ? pl + xa : pl - xb, tb = target_is_mean ? ph + xb : ph - xa;
+    const float glo = h.lo[d], ghi = h.lo[d] + h.cs[d] * h.n[d];
+    if (tb < glo || ta > ghi) return false;
+    c0 = cell_axis(h, d, ta);
+    c1 = cell_axis(h, d, tb);
+    return true;
+}
+// the pair (m, s) lies inside the Gaussian's cut box r at image kk.  (&, not &&: one test of
+// the three axes; short-circuited, each axis waits for its own LDS read of the staged candidate.)
+__device__ __forceinline__ bool in_cut_box(const float *m, const float *s, const float *r, const int *kk) {
+    bool mine = true;
+    for (int d = 0; d < 3; ++d) {
+        const float x = m[d] - s[d];
+        mine &= fabsf(x - 2.0f * kk[d]) <= r[d] + 1e-5f;
+    }
+    return mine;
 }
 
 // ------------------------------------------------------------------------------ forward
@@ -468,8 +526,75 @@ struct VCand {
     float v[CB];  // values of the launch's channel block
 };
 
-// COUNT (diagnostic, dgs_volume_count_pairs): instead of the outputs, counts[0] += the pairs
-// evaluated (candidates inside their cut box) and counts[1] += the live ones (G > 0).
+// The walk of one chunk (the wave's 64 samples s of cell cc, `active` lanes) over the small
+// Gaussians: fill(v, g) sets the staged candidate's values v[CB] of Gaussian g, and
+// eval(m, c, v) takes a candidate (mean, conic, staged values) that the lane keeps.
+template <int CB, class Fill, class Eval>
+__device__ __forceinline__ void walk_candidates(const Hdr &h, const Bin &bin, const float *__restrict__ conics,
+                                                VCand<CB> *cand, int lane, const int *cc, bool active,
+                                                const float *s, Fill fill, Eval eval) {
+    if (h.nsmall <= 0) return;
+    // the chunk's sample box (its cell's, widened by the rounding of the grid)
+    float bl[3], bh[3];
+    Win w[3];
+    for (int d = 0; d < 3; ++d) {
+        bl[d] = h.lo[d] + h.cs[d] * cc[d] - 1e-5f;
+        bh[d] = h.lo[d] + h.cs[d] * (cc[d] + 1) + 1e-5f;
+        if (cc[d] == 0) bl[d] = -INFINITY;  // (clamped cells hold everything below / above)
+        if (cc[d] == h.n[d] - 1) bh[d] = INFINITY;
+        float mn = INFINITY, mx = -INFINITY;
+        if (active) { mn = s[d]; mx = s[d]; }
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, o));
+            mx = fmaxf(mx, __shfl_xor(mx, o));
+        }
+        bl[d] = fmaxf(bl[d], mn);
+        bh[d] = fminf(bh[d], mx);
+        w[d] = box_images(h, d, bl[d], bh[d], h.E[d], true);
+    }
+    for (int cls = 0; cls < 2; ++cls)  // per class: its own reach
+    for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
+        for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
+            for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
+                const int kk[3] = {kx, ky, kz};
+                int c0[3], c1[3];
+                bool any = true;
+                for (int d = 0; d < 3 && any; ++d)  // the mean window
+                    any = window_cells(h, d, kk[d], h.Ec[cls][d], bl[d], bh[d], true, c0[d], c1[d]);
+                if (!any) continue;
+                for (int cz = c0[2]; cz <= c1[2]; ++cz)
+                    for (int cy = c0[1]; cy <= c1[1]; ++cy) {
+                        const int row = cls * h.ncells + (cz * h.n[1] + cy) * h.n[0];
+                        const int b = bin.gstart[row + c0[0]], e = bin.gstart[row + c1[0] + 1];
+                        for (int q0 = b; q0 < e; q0 += kWave) {
+                            const int q = q0 + lane;
+                            __syncthreads();
+                            if (q < e) {
+                                VCand<CB> v;
+                                v.mp = bin.gpk[q];
+                                v.ge = bin.gek[q];
+                                const int g = __float_as_int(v.mp.w);
+                                for (int k = 0; k < 6; ++k) v.c[k] = conics[(int64_t)g * 6 + k];
+                                fill(v.v, g);
+                                cand[lane] = v;
+                            }
+                            __syncthreads();
+                            const int cnt = min(kWave, e - q0);
+                            if (active)
+                                for (int u = 0; u < cnt; ++u) {
+                                    const float4 mp = cand[u].mp, ge = cand[u].ge;
+                                    const float m[3] = {mp.x, mp.y, mp.z};
+                                    const float r[3] = {ge.x, ge.y, ge.z};
+                                    if (in_cut_box(m, s, r, kk)) eval(m, cand[u].c, cand[u].v);
+                                }
+                        }
+                    }
+            }
+}
+
+// The C > 1 forward (C = 1: k_vol_forward_m), CB channels per launch.  COUNT (diagnostic,
+// dgs_volume_count_pairs): instead of the outputs, counts[0] += the pairs evaluated (candidates
+// inside their cut box) and counts[1] += the live ones (G > 0).
 template <int FN, int CB, bool COUNT = false>
 __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ buf, int P, int N, int C, int cbase,
                                                        const float *__restrict__ means,
@@ -479,36 +604,33 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
                                                        unsigned long long *__restrict__ counts = nullptr) {
     constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
     __shared__ VCand<CB> cand[kWave];
-    const Hdr h = hdr_of(buf);
+    const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
     const int nch = min(CB, C - cbase);
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+    if (vol_stale(buf, h, P, N)) {
         if (COUNT) return;
         for (int64_t j = (int64_t)blockIdx.x * kWave + lane; j < N; j += (int64_t)gridDim.x * kWave)
             for (int f = 0; f < K; ++f)
                 for (int ch = 0; ch < nch; ++ch) out[(j * K + f) * C + cbase + ch] = NAN;
         return;
     }
-    const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
-    const int32_t *__restrict__ sids = reinterpret_cast<const int32_t *>(buf + h.o_sids);
-    const int32_t *__restrict__ gstart = reinterpret_cast<const int32_t *>(buf + h.o_gstart);
-    const int32_t *__restrict__ sstart = reinterpret_cast<const int32_t *>(buf + h.o_sstart);
-    const float4 *__restrict__ gpk = reinterpret_cast<const float4 *>(buf + h.o_gpk);
-    const float4 *__restrict__ gek = reinterpret_cast<const float4 *>(buf + h.o_gek);
-
+    const Bin bin = bin_of(buf, h);
     for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
-        const int sb = sstart[cell], se = sstart[cell + 1];
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
         const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
         for (int j0 = sb; j0 < se; j0 += kWave) {
             const int j = j0 + lane;
             const bool active = j < se;
-            const int sid = active ? sids[j] : 0;
+            const int sid = active ? bin.sids[j] : 0;
             float s[3];
             for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
             float acc[KU][CB];
             for (int u = 0; u < KU; ++u)
                 for (int ch = 0; ch < CB; ++ch) acc[u][ch] = 0.0f;
             unsigned long long n_cand = 0, n_live = 0;
+            auto values_of = [&](float *vr, int g) {
+                for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
+            };
             auto eval = [&](const float *m, const float *c, const float *vr) {
                 float X[3], a[3], G, t[KU];
                 if constexpr (COUNT) {
@@ -523,89 +645,14 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
                     for (int u = 0; u < KU; ++u) acc[u][ch] += v * G * t[u];
                 }
             };
-            if (h.nsmall > 0) {
-                // the chunk's sample box (its cell's, widened by the rounding of the grid)
-                float bl[3], bh[3];
-                Win w[3];
-                for (int d = 0; d < 3; ++d) {
-                    bl[d] = h.lo[d] + h.cs[d] * cc[d] - 1e-5f;
-                    bh[d] = h.lo[d] + h.cs[d] * (cc[d] + 1) + 1e-5f;
-                    if (cc[d] == 0) bl[d] = -INFINITY;  // (clamped cells hold everything below / above)
-                    if (cc[d] == h.n[d] - 1) bh[d] = INFINITY;
-                    float mn = INFINITY, mx = -INFINITY;
-                    if (active) { mn = s[d]; mx = s[d]; }
-                    for (int o = kWave / 2; o > 0; o >>= 1) {
-                        mn = fminf(mn, __shfl_xor(mn, o));
-                        mx = fmaxf(mx, __shfl_xor(mx, o));
-                    }
-                    bl[d] = fmaxf(bl[d], mn);
-                    bh[d] = fminf(bh[d], mx);
-                    const float ghi = h.lo[d] + h.cs[d] * h.n[d];
-                    const Win wa = image_range(bl[d], h.E[d], h.lo[d], ghi, true);
-                    const Win wb = image_range(bh[d], h.E[d], h.lo[d], ghi, true);
-                    w[d].k0 = min(wa.k0, wb.k0);
-                    w[d].k1 = max(wa.k1, wb.k1);
-                }
-                for (int cls = 0; cls < 2; ++cls)  // per class: its own reach
-                for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
-                    for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
-                        for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
-                            const int kk[3] = {kx, ky, kz};
-                            int c0[3], c1[3];
-                            bool any = true;
-                            for (int d = 0; d < 3; ++d) {
-                                float xa, xb;
-                                image_window(kk[d], h.Ec[cls][d], xa, xb);
-                                const float ta = bl[d] + xa, tb = bh[d] + xb;  // mean window
-                                const float glo = h.lo[d], ghi = h.lo[d] + h.cs[d] * h.n[d];
-                                if (tb < glo || ta > ghi) { any = false; break; }
-                                c0[d] = cell_axis(h, d, ta);
-                                c1[d] = cell_axis(h, d, tb);
-                            }
-                            if (!any) continue;
-                            for (int cz = c0[2]; cz <= c1[2]; ++cz)
-                                for (int cy = c0[1]; cy <= c1[1]; ++cy) {
-                                    const int row = cls * h.ncells + (cz * h.n[1] + cy) * h.n[0];
-                                    const int b = gstart[row + c0[0]], e = gstart[row + c1[0] + 1];
-                                    for (int q0 = b; q0 < e; q0 += kWave) {
-                                        const int q = q0 + lane;
-                                        __syncthreads();
-                                        if (q < e) {
-                                            VCand<CB> v;
-                                            v.mp = gpk[q];
-                                            v.ge = gek[q];
-                                            const int g = __float_as_int(v.mp.w);
-                                            for (int k = 0; k < 6; ++k) v.c[k] = conics[(int64_t)g * 6 + k];
-                                            for (int ch = 0; ch < CB; ++ch)
-                                                v.v[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
-                                            cand[lane] = v;
-                                        }
-                                        __syncthreads();
-                                        const int cnt = min(kWave, e - q0);
-                                        if (active)
-                                            for (int u = 0; u < cnt; ++u) {
-                                                const float4 mp = cand[u].mp, ge = cand[u].ge;
-                                                const float m[3] = {mp.x, mp.y, mp.z};
-                                                const float r[3] = {ge.x, ge.y, ge.z};
-                                                bool mine = true;
-                                                for (int d = 0; d < 3; ++d) {  // inside its cut box at image kk
-                                                    const float x = m[d] - s[d];
-                                                    mine = mine && fabsf(x - 2.0f * kk[d]) <= r[d] + 1e-5f;
-                                                }
-                                                if (mine) eval(m, cand[u].c, cand[u].v);
-                                            }
-                                    }
-                                }
-                        }
-            }
+            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
             if (active) {
-                for (int q = gstart[2 * h.ncells]; q < gstart[2 * h.ncells + 1]; ++q) {  // big ones
-                    const int g = gids[q];
-                    float m[3], c[6];
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
+                    float m[3], c[6], vr[CB];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
-                    float vr[CB];
-                    for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
+                    values_of(vr, g);
                     eval(m, c, vr);
                 }
                 if constexpr (COUNT) {
@@ -639,11 +686,12 @@ __global__ __launch_bounds__(kBlock) void k_vol_hsum(int N, int C, const float *
 }
 
 // One pair's contribution to a Gaussian's gradient sums.  hrow: the sample's h row [KU][C]
-// (LDS or global).  CB == 1 means C == 1: phi, g and e are linear in h v0, so the pair uses h
-// alone and the caller scales the mean / conic sums by v0 once (bwd_store's scale).
+// (global).  CB == 1 means C == 1 (the big Gaussians): phi, g and e are
+// linear in h v0, so the pair uses h alone and the caller scales the mean / conic sums by v0 once
+// (bwd_store's scale).
 template <int FN, int CB>
 __device__ __forceinline__ void bwd_pair(const float *m, const float *c, const float *__restrict__ values, int g,
-                                         float v0, int C, int cbase, int nch, const float *s, const float *hrow,
+                                         int C, int cbase, int nch, const float *s, const float *hrow,
                                          float *dm, float *dc, float *dv) {
     constexpr int KU = VTr<FN>::KU;
     float X[3], a[3], G, t[KU];
@@ -823,7 +871,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
     const Hdr h = hdr_of(buf);
     const int lane = threadIdx.x;
     const int nch = min(CB, C - cbase);
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+    if (vol_stale(buf, h, P, N)) {  // stale buffer / inputs: loud
         const float nan[9] = {NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN};
         for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < P; i += (int64_t)gridDim.x * kWave)
             bwd_store<CB>((int)i, C, cbase, nch, nan, nan, nan, dmeans, dvalues, dconics);
@@ -919,7 +967,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
                                                 if constexpr (CB == 1)
                                                     bwd_pair_t<FN>(m, c, c2, sv, &shrow[u][0], mom);
                                                 else
-                                                    bwd_pair<FN, CB>(m, c, values, g, v0, C, cbase, nch, sv,
+                                                    bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sv,
                                                                      hs + (int64_t)__float_as_int(sp.w) * KU * C, dm,
                                                                      dc, dv);
                                             }
@@ -947,7 +995,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
     constexpr int NV = 9 + CB;
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) return;  // (k_vol_backward flags it)
+    if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward writes the NaN)
     const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
     const int nch = min(CB, C - cbase);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -960,7 +1008,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
         for (int k = 0; k < NV; ++k) v[k] = 0.0f;
         for (int sid = threadIdx.x; sid < N; sid += kBlock) {
             const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
-            bwd_pair<FN, CB>(m, c, values, g, CB == 1 ? values[g] : 0.0f, C, cbase, nch, sp,
+            bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sp,
                              hs + (int64_t)sid * VTr<FN>::KU * C, v, v + 3, v + 9);
         }
         for (int k = 0; k < NV; ++k)
@@ -980,26 +1028,21 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
     }
 }
 
-// ------------------------------------------------------------------------------ fused functions
-// Several of the four functions of one field at the same samples (C = 1; DESIGN.md 4.8, "fused
-// functions"): one walk of the candidates, one pair_eval per kept pair, for every function of
-// MASK (bit f = function f).  The walks are those of k_vol_forward<FN, 1> / k_vol_backward<FN, 1>.
-__host__ __device__ constexpr int mask_ku(int mask) {
-    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0);
-}
-// offset of function f's unique components in a concatenated row of the mask's functions
-__host__ __device__ constexpr int mask_off(int mask, int f) { return mask_ku(mask & ((1 << f) - 1)); }
-__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & 4 ? 2 : mask & 2 ? 1 : 0; }
-
+// ------------------------------------------------------------------------------ C = 1: function masks
+// One or several of the four functions of one field at the same samples (C = 1; DESIGN.md 4.8,
+// "fused functions"): one walk of the candidates, one pair_eval per kept pair, for every function
+// of MASK (bit f = function f).  The single-function forward at C = 1 is the single-bit mask, so
+// a fused output equals the single call's by construction; the backward of one function is
+// k_vol_backward<FN, 1>, of several k_vol_backward_m.
 struct VOuts {
     float *p[4];  // per function code; entries outside the mask unused
 };
 
-// acc[u] += v G t_u for function FN with the roundings k_vol_forward<FN, 1> has as compiled, written
-// out so that a fused output equals the single call's bit for bit: among the staged candidates
-// the sum is fma(v, G, acc) for the gaussian and fma(round(v G), t_u, acc) for the others; among
-// the big Gaussians (BIG) the product is loop-invariant there, so it is rounded on its own and
-// then added ("fused functions").
+// acc[u] += v G t_u for function FN: the definition of the C = 1 forward sum, with every rounding
+// written out so that it does not depend on what else the kernel computes (the other functions
+// of a mask share v, G and a).  Among the staged candidates the sum is fma(v, G, acc) for the
+// gaussian and fma(round(v G), t_u, acc) for the others; among the big Gaussians (BIG) the
+// product round(round(v G) t_u) is rounded on its own and then added.
 template <int FN, bool BIG>
 __device__ __forceinline__ void fwd_acc(float v, float G, const float *a, const float *c, float *acc) {
     constexpr int KU = VTr<FN>::KU;
@@ -1035,9 +1078,9 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
     constexpr int SKU = mask_ku(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
     __shared__ VCand<1> cand[kWave];
-    const Hdr &h = hdr_of(buf);  // read in place: a local copy indexed by the axis would live in scratch
+    const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+    if (vol_stale(buf, h, P, N)) {
         for (int64_t j = (int64_t)blockIdx.x * kWave + lane; j < N; j += (int64_t)gridDim.x * kWave) {
             if constexpr ((MASK & 1) != 0) fwd_nan<0>(outs.p[0], j);
             if constexpr ((MASK & 2) != 0) fwd_nan<1>(outs.p[1], j);
@@ -1046,20 +1089,14 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
         }
         return;
     }
-    const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
-    const int32_t *__restrict__ sids = reinterpret_cast<const int32_t *>(buf + h.o_sids);
-    const int32_t *__restrict__ gstart = reinterpret_cast<const int32_t *>(buf + h.o_gstart);
-    const int32_t *__restrict__ sstart = reinterpret_cast<const int32_t *>(buf + h.o_sstart);
-    const float4 *__restrict__ gpk = reinterpret_cast<const float4 *>(buf + h.o_gpk);
-    const float4 *__restrict__ gek = reinterpret_cast<const float4 *>(buf + h.o_gek);
-
+    const Bin bin = bin_of(buf, h);
     for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
-        const int sb = sstart[cell], se = sstart[cell + 1];
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
         const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
         for (int j0 = sb; j0 < se; j0 += kWave) {
             const int j = j0 + lane;
             const bool active = j < se;
-            const int sid = active ? sids[j] : 0;
+            const int sid = active ? bin.sids[j] : 0;
             float s[3];
             for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
             float acc[SKU];
@@ -1073,83 +1110,12 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 4) != 0) fwd_acc<2, BIG>(v, G, a, c, acc + O2);
                 if constexpr ((MASK & 8) != 0) fwd_acc<3, BIG>(v, G, a, c, acc + O3);
             };
-            if (h.nsmall > 0) {
-                // the chunk's sample box (its cell's, widened by the rounding of the grid)
-                float bl[3], bh[3];
-                Win w[3];
-                for (int d = 0; d < 3; ++d) {
-                    bl[d] = h.lo[d] + h.cs[d] * cc[d] - 1e-5f;
-                    bh[d] = h.lo[d] + h.cs[d] * (cc[d] + 1) + 1e-5f;
-                    if (cc[d] == 0) bl[d] = -INFINITY;  // (clamped cells hold everything below / above)
-                    if (cc[d] == h.n[d] - 1) bh[d] = INFINITY;
-                    float mn = INFINITY, mx = -INFINITY;
-                    if (active) { mn = s[d]; mx = s[d]; }
-                    for (int o = kWave / 2; o > 0; o >>= 1) {
-                        mn = fminf(mn, __shfl_xor(mn, o));
-                        mx = fmaxf(mx, __shfl_xor(mx, o));
-                    }
-                    bl[d] = fmaxf(bl[d], mn);
-                    bh[d] = fminf(bh[d], mx);
-                    const float ghi = h.lo[d] + h.cs[d] * h.n[d];
-                    const Win wa = image_range(bl[d], h.E[d], h.lo[d], ghi, true);
-                    const Win wb = image_range(bh[d], h.E[d], h.lo[d], ghi, true);
-                    w[d].k0 = min(wa.k0, wb.k0);
-                    w[d].k1 = max(wa.k1, wb.k1);
-                }
-                for (int cls = 0; cls < 2; ++cls)  // per class: its own reach
-                for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
-                    for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
-                        for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
-                            const int kk[3] = {kx, ky, kz};
-                            int c0[3], c1[3];
-                            bool any = true;
-                            for (int d = 0; d < 3; ++d) {
-                                float xa, xb;
-                                image_window(kk[d], h.Ec[cls][d], xa, xb);
-                                const float ta = bl[d] + xa, tb = bh[d] + xb;  // mean window
-                                const float glo = h.lo[d], ghi = h.lo[d] + h.cs[d] * h.n[d];
-                                if (tb < glo || ta > ghi) { any = false; break; }
-                                c0[d] = cell_axis(h, d, ta);
-                                c1[d] = cell_axis(h, d, tb);
-                            }
-                            if (!any) continue;
-                            for (int cz = c0[2]; cz <= c1[2]; ++cz)
-                                for (int cy = c0[1]; cy <= c1[1]; ++cy) {
-                                    const int row = cls * h.ncells + (cz * h.n[1] + cy) * h.n[0];
-                                    const int b = gstart[row + c0[0]], e = gstart[row + c1[0] + 1];
-                                    for (int q0 = b; q0 < e; q0 += kWave) {
-                                        const int q = q0 + lane;
-                                        __syncthreads();
-                                        if (q < e) {
-                                            VCand<1> v;
-                                            v.mp = gpk[q];
-                                            v.ge = gek[q];
-                                            const int g = __float_as_int(v.mp.w);
-                                            for (int k = 0; k < 6; ++k) v.c[k] = conics[(int64_t)g * 6 + k];
-                                            v.v[0] = values[g];
-                                            cand[lane] = v;
-                                        }
-                                        __syncthreads();
-                                        const int cnt = min(kWave, e - q0);
-                                        if (active)
-                                            for (int u = 0; u < cnt; ++u) {
-                                                const float4 mp = cand[u].mp, ge = cand[u].ge;
-                                                const float m[3] = {mp.x, mp.y, mp.z};
-                                                const float r[3] = {ge.x, ge.y, ge.z};
-                                                bool mine = true;
-                                                for (int d = 0; d < 3; ++d) {  // inside its cut box at image kk
-                                                    const float x = m[d] - s[d];
-                                                    mine = mine && fabsf(x - 2.0f * kk[d]) <= r[d] + 1e-5f;
-                                                }
-                                                if (mine) eval(m, cand[u].c, cand[u].v[0], std::false_type{});
-                                            }
-                                    }
-                                }
-                        }
-            }
+            walk_candidates<1>(
+                h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
+                [&](const float *m, const float *c, const float *vr) { eval(m, c, vr[0], std::false_type{}); });
             if (active) {
-                for (int q = gstart[2 * h.ncells]; q < gstart[2 * h.ncells + 1]; ++q) {  // big ones
-                    const int g = gids[q];
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
                     float m[3], c[6];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
@@ -1210,7 +1176,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
     __shared__ float shrow[kWave][SKU];  // the candidates' H rows, function after function
     const Hdr &h = hdr_of(buf);  // (in place, as k_vol_forward_m)
     const int lane = threadIdx.x;
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) {  // stale buffer / inputs: loud
+    if (vol_stale(buf, h, P, N)) {  // stale buffer / inputs: loud
         const float nan[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
         for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < P; i += (int64_t)gridDim.x * kWave)
             bwd_store<1>((int)i, 1, 0, 1, nan, nan, nan, dmeans, dvalues, dconics);
@@ -1338,7 +1304,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
     constexpr int NV = 10, SKU = mask_ku(MASK);
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
-    if (h.magic != kVolMagic || h.P != P || h.N != N || vol_flagged(buf, h)) return;  // (k_vol_backward_m flags it)
+    if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_m writes the NaN)
     const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     for (int b = blockIdx.x; b < h.nbig; b += gridDim.x) {
@@ -1353,13 +1319,13 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
             const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
             const float *hrow = hs + (int64_t)sid * SKU;
             if constexpr ((MASK & 1) != 0)
-                bwd_pair<0, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 0), v, v + 3, v + 9);
+                bwd_pair<0, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 0), v, v + 3, v + 9);
             if constexpr ((MASK & 2) != 0)
-                bwd_pair<1, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 1), v, v + 3, v + 9);
+                bwd_pair<1, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 1), v, v + 3, v + 9);
             if constexpr ((MASK & 4) != 0)
-                bwd_pair<2, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
+                bwd_pair<2, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
             if constexpr ((MASK & 8) != 0)
-                bwd_pair<3, 1>(m, c, values, g, v0, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
+                bwd_pair<3, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
         }
         for (int k = 0; k < NV; ++k)
             for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
@@ -1378,12 +1344,20 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
     }
 }
 
+// ------------------------------------------------------------------------------ launches
+struct VArgs {  // what every launch takes
+    const char *buf;
+    int P, N, C;
+    const float *means, *values, *conics, *samples;
+    hipStream_t s;
+};
+
+// C = 1: every function mask
 template <int MASK>
-static void launch_fwd_m(const char *buf, int P, int N, const float *means, const float *values,
-                         const float *conics, const float *samples, float *const *outs, hipStream_t s) {
+static void launch_fwd_m(const VArgs &a, float *const *outs) {
     VOuts o;
     for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? outs[f] : nullptr;
-    k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, s>>>(buf, P, N, means, values, conics, samples, o);
+    k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, o);
 }
 template <int FN>
 static void launch_hsum_cat(int mask, int N, const float *const *dLs, float *hs, hipStream_t s) {
@@ -1392,65 +1366,45 @@ static void launch_hsum_cat(int mask, int N, const float *const *dLs, float *hs,
                                                                                  mask_off(mask, FN));
 }
 template <int MASK>
-static void launch_bwd_m(const char *buf, int P, int N, const float *means, const float *values,
-                         const float *conics, const float *samples, const float *const *dLs, float *hs, float *dm,
-                         float *dv, float *dc, hipStream_t s) {
-    launch_hsum_cat<0>(MASK, N, dLs, hs, s);
-    launch_hsum_cat<1>(MASK, N, dLs, hs, s);
-    launch_hsum_cat<2>(MASK, N, dLs, hs, s);
-    launch_hsum_cat<3>(MASK, N, dLs, hs, s);
-    k_vol_backward_m<MASK><<<kVolBwdBlocks, kWave, 0, s>>>(buf, P, N, means, values, conics, samples, hs, dm, dv, dc);
-    k_vol_backward_big_m<MASK><<<256, kBlock, 0, s>>>(buf, P, N, means, values, conics, samples, hs, dm, dv, dc);
+static void launch_bwd_m(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc) {
+    launch_hsum_cat<0>(MASK, a.N, dLs, hs, a.s);
+    launch_hsum_cat<1>(MASK, a.N, dLs, hs, a.s);
+    launch_hsum_cat<2>(MASK, a.N, dLs, hs, a.s);
+    launch_hsum_cat<3>(MASK, a.N, dLs, hs, a.s);
+    k_vol_backward_m<MASK><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples,
+                                                             hs, dm, dv, dc);
+    k_vol_backward_big_m<MASK><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, hs,
+                                                        dm, dv, dc);
 }
 
-// the 11 masks of two or more functions
-#define DGS_VOL_MASKS(X) X(3) X(5) X(6) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
-
-static int vol_cb(int C) { return C <= 1 ? 1 : C <= 4 ? 4 : 8; }
-
+// one function, CB = 1 (the backward at C = 1), 4 (C <= 4) or 8 channels per launch
 template <int FN, int CB>
-static void launch_fwd(const char *buf, int P, int N, int C, const float *means, const float *values,
-                       const float *conics, const float *samples, float *out, hipStream_t s) {
-    for (int cb = 0; cb < C; cb += CB)
-        k_vol_forward<FN, CB><<<kVolFwdBlocks, kWave, 0, s>>>(
-            buf, P, N, C, cb, means, values, conics, samples, out);
+static void launch_fwd(const VArgs &a, float *out) {
+    for (int cb = 0; cb < a.C; cb += CB)
+        k_vol_forward<FN, CB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
+                                                                a.samples, out);
 }
 template <int FN, int CB>
-static void launch_bwd(const char *buf, int P, int N, int C, const float *means, const float *values,
-                       const float *conics, const float *samples, const float *dL, float *hs, float *dm,
-                       float *dv, float *dc, hipStream_t s) {
-    const int64_t nh = (int64_t)N * C;
-    if (nh > 0) k_vol_hsum<FN><<<(unsigned)((nh + kBlock - 1) / kBlock), kBlock, 0, s>>>(N, C, dL, hs);
-    for (int cb = 0; cb < C; cb += CB) {
-        if (P > 0)
-            k_vol_backward<FN, CB><<<kVolBwdBlocks, kWave, 0, s>>>(buf, P, N, C, cb, means, values, conics, samples,
-                                                                   hs, dm, dv, dc);
-        k_vol_backward_big<FN, CB><<<256, kBlock, 0, s>>>(buf, P, N, C, cb, means, values, conics, samples, hs,
-                                                           dm, dv, dc);
+static void launch_bwd(const VArgs &a, const float *dL, float *hs, float *dm, float *dv, float *dc) {
+    const int64_t nh = (int64_t)a.N * a.C;
+    k_vol_hsum<FN><<<(unsigned)((nh + kBlock - 1) / kBlock), kBlock, 0, a.s>>>(a.N, a.C, dL, hs);
+    for (int cb = 0; cb < a.C; cb += CB) {
+        k_vol_backward<FN, CB><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values,
+                                                                 a.conics, a.samples, hs, dm, dv, dc);
+        k_vol_backward_big<FN, CB><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
+                                                            a.samples, hs, dm, dv, dc);
     }
 }
 
-template <int FN>
-static void dispatch_fwd(int C, const char *buf, int P, int N, const float *m, const float *v, const float *c,
-                         const float *sm, float *out, hipStream_t s) {
-    switch (vol_cb(C)) {
-        case 1: launch_fwd<FN, 1>(buf, P, N, C, m, v, c, sm, out, s); break;
-        case 4: launch_fwd<FN, 4>(buf, P, N, C, m, v, c, sm, out, s); break;
-        default: launch_fwd<FN, 8>(buf, P, N, C, m, v, c, sm, out, s); break;
-    }
-}
-template <int FN>
-static void dispatch_bwd(int C, const char *buf, int P, int N, const float *m, const float *v, const float *c,
-                         const float *sm, const float *dL, float *hs, float *dm, float *dv, float *dc,
-                         hipStream_t s) {
-    switch (vol_cb(C)) {
-        case 1: launch_bwd<FN, 1>(buf, P, N, C, m, v, c, sm, dL, hs, dm, dv, dc, s); break;
-        case 4: launch_bwd<FN, 4>(buf, P, N, C, m, v, c, sm, dL, hs, dm, dv, dc, s); break;
-        default: launch_bwd<FN, 8>(buf, P, N, C, m, v, c, sm, dL, hs, dm, dv, dc, s); break;
-    }
-}
+// the masks of the forward kernels (all 15) and of the fused backward (two or more functions)
+#define DGS_VOL_MASKS_FUSED(X) X(3) X(5) X(6) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+#define DGS_VOL_MASKS(X) X(1) X(2) X(4) X(8) DGS_VOL_MASKS_FUSED(X)
 
-static const int kKU[4] = {1, 3, 6, 10};
+// the function of a single-bit mask and its channel block: case label FN * 3 + {0: CB 1, 1: CB 4, 2: CB 8}
+static int fn_cb_case(int mask, int C) { return mask_top(mask) * 3 + (C <= 1 ? 0 : C <= 4 ? 1 : 2); }
+#define DGS_VOL_FN_C1(X) X(0, 1) X(1, 1) X(2, 1) X(3, 1)
+#define DGS_VOL_FN_CB(X) X(0, 4) X(0, 8) X(1, 4) X(1, 8) X(2, 4) X(2, 8) X(3, 4) X(3, 8)
+#define DGS_VOL_FN_CB_CASE(FN, CB) FN * 3 + (CB == 1 ? 0 : CB == 4 ? 1 : 2)
 
 }  // namespace vol
 }  // namespace dgs
@@ -1573,9 +1527,37 @@ extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const flo
     return DGS_OK;
 }
 
+// ---- the calls (include/dgs_volume.h).  A function is the single-bit mask 1 << function; a
+// function code out of range becomes mask 0, which vol_check refuses.
+static int fn_mask(int function) { return function < 0 || function > 3 ? 0 : 1 << function; }
+
+static size_t vol_workspace(int mask, int N, int C, int backward) {
+    const bool one = mask == 1 || mask == 2 || mask == 4 || mask == 8;
+    if (mask < 1 || mask > 15 || !backward || N <= 0 || C <= 0 || (!one && C != 1)) return 0;
+    return (size_t)N * mask_ku(mask) * C * 4;  // hs[N][unique components][C]
+}
+extern "C" size_t dgs_volume_workspace_size(int function, int P, int N, int C, int backward) {
+    return vol_workspace(fn_mask(function), N, C, backward);
+}
+extern "C" size_t dgs_volume_workspace_size_multi(int mask, int P, int N, int C, int backward) {
+    return vol_workspace(mask, N, C, backward);
+}
+
+// multi: the call came through a *_multi entry (the messages name what that caller passed)
+static int vol_check(bool multi, int mask, int P, int N, int C, const void *binning, size_t bytes) {
+    if (mask < 1 || mask > 15)
+        return fail(DGS_ERR_ARG, multi ? "dgs_volume_*_multi: mask must be 1..15" : "dgs_volume: function must be 0..3");
+    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
+    if ((mask & (mask - 1)) != 0 && C != 1)
+        return fail(DGS_ERR_ARG,
+                    "dgs_volume_*_multi: several functions need C = 1; call the per-function entry points and add");
+    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+    return DGS_OK;
+}
+
 // The call-time check of k_vol_verify (the header's offsets are read on the device).
 static int vol_flag_reset_verify(int P, int N, const float *means, const float *conics, const float *samples,
-                                 const void *binning, size_t bytes, hipStream_t s) {
+                                 const void *binning, hipStream_t s) {
     char *buf = static_cast<char *>(const_cast<void *>(binning));
     const int64_t n = (int64_t)P * 9 + (int64_t)N * 3;
     const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((n + kBlock - 1) / kBlock, 1), 2048);
@@ -1584,38 +1566,79 @@ static int vol_flag_reset_verify(int P, int N, const float *means, const float *
                                            reinterpret_cast<const uint32_t *>(conics),
                                            reinterpret_cast<const uint32_t *>(samples), buf);
     DGS_TRY_HIP(hipGetLastError());
-    (void)bytes;
     return DGS_OK;
 }
 
-extern "C" size_t dgs_volume_workspace_size(int function, int P, int N, int C, int backward) {
-    if (!backward || function < 0 || function > 3 || N <= 0 || C <= 0) return 0;
-    return (size_t)N * kKU[function] * C * 4;
+static int vol_forward(bool multi, int mask, int P, int N, int C, const float *means, const float *values, const float *conics,
+                       const float *samples, const void *binning, size_t binning_bytes, float *const *outs,
+                       dgs_stream_t stream, int debug) {
+    if (int rc = vol_check(multi, mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_multi: outs required");
+    if (N == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {  // every mask, a single function included
+        switch (mask) {
+#define X(M) case M: launch_fwd_m<M>(a, outs); break;
+            DGS_VOL_MASKS(X)
+#undef X
+        }
+    } else {  // (vol_check: a single function)
+        switch (fn_cb_case(mask, C)) {
+#define X(FN, CB) case DGS_VOL_FN_CB_CASE(FN, CB): launch_fwd<FN, CB>(a, outs[FN]); break;
+            DGS_VOL_FN_CB(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
 }
 
-static int vol_check(int function, int P, int N, int C, const void *binning, size_t bytes) {
-    if (function < 0 || function > 3) return fail(DGS_ERR_ARG, "dgs_volume: function must be 0..3");
-    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
-    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+static int vol_backward(bool multi, int mask, int P, int N, int C, const float *means, const float *values, const float *conics,
+                        const float *samples, const float *const *dLs, const void *binning, size_t binning_bytes,
+                        float *dm, float *dv, float *dc, void *workspace, size_t workspace_bytes,
+                        dgs_stream_t stream, int debug) {
+    if (int rc = vol_check(multi, mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!dLs) return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: dL_douts required");
+    if (workspace_bytes < vol_workspace(mask, N, C, 1))
+        return fail(DGS_ERR_ARG, multi ? "dgs_volume_backward_multi: workspace too small"
+                                       : "dgs_volume_backward: workspace too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) return DGS_OK;
+    if (N == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dm, 0, (size_t)P * 12, s));
+        DGS_TRY_HIP(hipMemsetAsync(dv, 0, (size_t)P * C * 4, s));
+        DGS_TRY_HIP(hipMemsetAsync(dc, 0, (size_t)P * 24, s));
+        return DGS_OK;
+    }
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    float *hs = static_cast<float *>(workspace);
+    if ((mask & (mask - 1)) != 0) {  // several functions (C = 1)
+        switch (mask) {
+#define X(M) case M: launch_bwd_m<M>(a, dLs, hs, dm, dv, dc); break;
+            DGS_VOL_MASKS_FUSED(X)
+#undef X
+        }
+    } else {
+        switch (fn_cb_case(mask, C)) {
+#define X(FN, CB) case DGS_VOL_FN_CB_CASE(FN, CB): launch_bwd<FN, CB>(a, dLs[FN], hs, dm, dv, dc); break;
+            DGS_VOL_FN_C1(X) DGS_VOL_FN_CB(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
     return DGS_OK;
 }
 
 extern "C" int dgs_volume_forward(int function, int P, int N, int C, const float *means, const float *values,
                                   const float *conics, const float *samples, const void *binning,
                                   size_t binning_bytes, float *out, dgs_stream_t stream, int debug) {
-    if (int rc = vol_check(function, P, N, C, binning, binning_bytes)) return rc;
-    if (N == 0) return DGS_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const char *buf = static_cast<const char *>(binning);
-    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
-    switch (function) {
-        case 0: dispatch_fwd<0>(C, buf, P, N, means, values, conics, samples, out, s); break;
-        case 1: dispatch_fwd<1>(C, buf, P, N, means, values, conics, samples, out, s); break;
-        case 2: dispatch_fwd<2>(C, buf, P, N, means, values, conics, samples, out, s); break;
-        default: dispatch_fwd<3>(C, buf, P, N, means, values, conics, samples, out, s); break;
-    }
-    DGS_LAUNCH_CHECK(s, debug);
-    return DGS_OK;
+    float *outs[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (fn_mask(function)) outs[function] = out;
+    return vol_forward(false, fn_mask(function), P, N, C, means, values, conics, samples, binning, binning_bytes, outs,
+                       stream, debug);
 }
 
 extern "C" int dgs_volume_backward(int function, int P, int N, int C, const float *means, const float *values,
@@ -1623,74 +1646,16 @@ extern "C" int dgs_volume_backward(int function, int P, int N, int C, const floa
                                    const void *binning, size_t binning_bytes, float *dL_dmeans, float *dL_dvalues,
                                    float *dL_dconics, void *workspace, size_t workspace_bytes, dgs_stream_t stream,
                                    int debug) {
-    if (int rc = vol_check(function, P, N, C, binning, binning_bytes)) return rc;
-    if (workspace_bytes < dgs_volume_workspace_size(function, P, N, C, 1))
-        return fail(DGS_ERR_ARG, "dgs_volume_backward: workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (P == 0) return DGS_OK;
-    if (N == 0) {
-        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
-        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * C * 4, s));
-        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
-        return DGS_OK;
-    }
-    const char *buf = static_cast<const char *>(binning);
-    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
-    float *hs = static_cast<float *>(workspace);
-    switch (function) {
-        case 0: dispatch_bwd<0>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
-        case 1: dispatch_bwd<1>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
-        case 2: dispatch_bwd<2>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
-        default: dispatch_bwd<3>(C, buf, P, N, means, values, conics, samples, dL_dout, hs, dL_dmeans, dL_dvalues, dL_dconics, s); break;
-    }
-    DGS_LAUNCH_CHECK(s, debug);
-    return DGS_OK;
-}
-
-// ---- fused functions (include/dgs_volume.h) ----
-static int vol_mask_single(int mask) {  // the function of a single-bit mask, else -1
-    return mask == 1 ? 0 : mask == 2 ? 1 : mask == 4 ? 2 : mask == 8 ? 3 : -1;
-}
-
-static int vol_check_multi(int mask, int P, int N, int C, const void *binning, size_t bytes) {
-    if (mask < 1 || mask > 15) return fail(DGS_ERR_ARG, "dgs_volume_*_multi: mask must be 1..15");
-    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
-    if (vol_mask_single(mask) < 0 && C != 1)
-        return fail(DGS_ERR_ARG,
-                    "dgs_volume_*_multi: several functions need C = 1; call the per-function entry points and add");
-    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
-    return DGS_OK;
-}
-
-extern "C" size_t dgs_volume_workspace_size_multi(int mask, int P, int N, int C, int backward) {
-    if (mask < 1 || mask > 15) return 0;
-    const int f = vol_mask_single(mask);
-    if (f >= 0) return dgs_volume_workspace_size(f, P, N, C, backward);
-    if (!backward || N <= 0 || C != 1) return 0;
-    return (size_t)N * mask_ku(mask) * 4;
+    const float *dLs[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (fn_mask(function)) dLs[function] = dL_dout;
+    return vol_backward(false, fn_mask(function), P, N, C, means, values, conics, samples, dLs, binning, binning_bytes,
+                        dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
 }
 
 extern "C" int dgs_volume_forward_multi(int mask, int P, int N, int C, const float *means, const float *values,
                                         const float *conics, const float *samples, const void *binning,
                                         size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug) {
-    if (int rc = vol_check_multi(mask, P, N, C, binning, binning_bytes)) return rc;
-    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_multi: outs required");
-    const int f = vol_mask_single(mask);
-    if (f >= 0)
-        return dgs_volume_forward(f, P, N, C, means, values, conics, samples, binning, binning_bytes, outs[f], stream,
-                                  debug);
-    if (N == 0) return DGS_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const char *buf = static_cast<const char *>(binning);
-    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
-    switch (mask) {
-#define X(M) case M: launch_fwd_m<M>(buf, P, N, means, values, conics, samples, outs, s); break;
-        DGS_VOL_MASKS(X)
-#undef X
-        default: return fail(DGS_ERR_ARG, "dgs_volume_forward_multi: mask");
-    }
-    DGS_LAUNCH_CHECK(s, debug);
-    return DGS_OK;
+    return vol_forward(true, mask, P, N, C, means, values, conics, samples, binning, binning_bytes, outs, stream, debug);
 }
 
 extern "C" int dgs_volume_backward_multi(int mask, int P, int N, int C, const float *means, const float *values,
@@ -1698,43 +1663,14 @@ extern "C" int dgs_volume_backward_multi(int mask, int P, int N, int C, const fl
                                          const void *binning, size_t binning_bytes, float *dL_dmeans,
                                          float *dL_dvalues, float *dL_dconics, void *workspace,
                                          size_t workspace_bytes, dgs_stream_t stream, int debug) {
-    if (int rc = vol_check_multi(mask, P, N, C, binning, binning_bytes)) return rc;
-    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: dL_douts required");
-    const int f = vol_mask_single(mask);
-    if (f >= 0)
-        return dgs_volume_backward(f, P, N, C, means, values, conics, samples, dL_douts[f], binning, binning_bytes,
-                                   dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
-    if (workspace_bytes < dgs_volume_workspace_size_multi(mask, P, N, C, 1))
-        return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: workspace too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (P == 0) return DGS_OK;
-    if (N == 0) {
-        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
-        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * 4, s));
-        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
-        return DGS_OK;
-    }
-    const char *buf = static_cast<const char *>(binning);
-    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
-    float *hs = static_cast<float *>(workspace);
-    switch (mask) {
-#define X(M)                                                                                                      \
-    case M:                                                                                                       \
-        launch_bwd_m<M>(buf, P, N, means, values, conics, samples, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics, \
-                        s);                                                                                       \
-        break;
-        DGS_VOL_MASKS(X)
-#undef X
-        default: return fail(DGS_ERR_ARG, "dgs_volume_backward_multi: mask");
-    }
-    DGS_LAUNCH_CHECK(s, debug);
-    return DGS_OK;
+    return vol_backward(true, mask, P, N, C, means, values, conics, samples, dL_douts, binning, binning_bytes, dL_dmeans,
+                        dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
 }
 
 extern "C" int dgs_volume_count_pairs(int P, int N, const float *means, const float *conics, const float *samples,
                                       const void *binning, size_t binning_bytes, int64_t *counts,
                                       dgs_stream_t stream) {
-    if (int rc = vol_check(0, P, N, 1, binning, binning_bytes)) return rc;
+    if (int rc = vol_check(false, 1, P, N, 1, binning, binning_bytes)) return rc;
     if (!counts) return fail(DGS_ERR_ARG, "dgs_volume_count_pairs: counts required");
     counts[0] = counts[1] = 0;
     if (N == 0 || P == 0) return DGS_OK;
@@ -1743,7 +1679,7 @@ extern "C" int dgs_volume_count_pairs(int P, int N, const float *means, const fl
     note_internal_alloc();  // (a diagnostic)
     DGS_TRY_HIP(hipMallocAsync(reinterpret_cast<void **>(&d), 24, s));
     DGS_TRY_HIP(hipMemsetAsync(d, 0, 24, s));
-    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, binning_bytes, s)) return rc;
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
     // values are not read in COUNT mode; conics stand in for the pointer
     k_vol_forward<0, 1, true><<<kVolFwdBlocks, kWave, 0, s>>>(static_cast<const char *>(binning), P, N, 1, 0, means,
                                                               conics, conics, samples, nullptr, d);

@@ -97,6 +97,74 @@ def test_volume_seams_and_images(dgs):
         _check(f, means, values, conics, samples, seed=f)
 
 
+@pytest.mark.parametrize("C", [1, 3, 9])
+def test_volume_chunk_boundaries(dgs, C):
+    """The construction of test_gpu_volume_multi.test_fused_chunk_boundaries through the single
+    calls: 150 Gaussians and 200 samples inside a box of side 0.004 (one grid cell) next to a
+    sparse remainder, so a cell row holds two full 64-wide batches and a partial one in the
+    lane = sample and the lane = Gaussian loops.  C = 1 is the C = 1 kernels of both, C = 3 one
+    launch of 4 channels, C = 9 two launches of 8."""
+    rng = np.random.default_rng(21)
+    means, values, _, conics = _field(250, C, 5)
+    samples = vo.samples3(330, seed=13)
+    centre = np.array([0.31, -0.22, 0.47])
+    means[:150] = (centre + rng.uniform(-0.002, 0.002, (150, 3))).astype(np.float32)
+    samples[:200] = (centre + rng.uniform(-0.002, 0.002, (200, 3))).astype(np.float32)
+    for f in range(4):
+        _check(f, means, values, conics, samples, seed=f)
+
+
+@pytest.mark.parametrize("function", [0, 1, 2, 3])
+def test_volume_single_mask_is_the_single_call(dgs, function):
+    """At C = 1 the C entry dgs_volume_{forward,backward}_multi with the single-bit mask 1 << f
+    gives the outputs and gradients of dgs_volume_{forward,backward}(f) bit for bit, on the parity
+    field of test_gpu_volume_multi.py.  Both are called through ctypes on libdgs.so: the extension
+    itself sends a single code to the single entry."""
+    import ctypes
+    import os
+    from diff_gaussian_sampling import _C
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(_C.__file__), "libdgs.so"))
+    VP, SZ, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    lib.dgs_volume_forward.argtypes = [I] * 4 + [VP] * 5 + [SZ, VP, VP, I]
+    lib.dgs_volume_forward_multi.argtypes = [I] * 4 + [VP] * 5 + [SZ, VP, VP, I]
+    lib.dgs_volume_backward.argtypes = [I] * 4 + [VP] * 6 + [SZ] + [VP] * 4 + [SZ, VP, I]
+    lib.dgs_volume_backward_multi.argtypes = [I] * 4 + [VP] * 6 + [SZ] + [VP] * 4 + [SZ, VP, I]
+    for fn in (lib.dgs_volume_workspace_size, lib.dgs_volume_workspace_size_multi):
+        fn.restype, fn.argtypes = SZ, [I] * 5
+    dev = torch.device("cuda:0")
+    means, values, _, conics = vo.gaussians3(1000, 1, seed=3, scale=0.009 * 1000 ** (1 / 3))
+    m, v, c, s = (torch.from_numpy(x).to(dev) for x in (means, values, conics, vo.samples3(2000, seed=12)))
+    P, N, K, mask = m.shape[0], s.shape[0], 3 ** function, 1 << function
+    buf = _C.volume_preprocess(m, c, s, False)
+    torch.cuda.synchronize()  # (the calls below run on the null stream)
+    ptr = [t.data_ptr() for t in (m, v, c, s)]
+    nan = float("nan")
+
+    out, multi = (torch.full((N, K), nan, device=dev) for _ in range(2))
+    assert lib.dgs_volume_forward(function, P, N, 1, *ptr, buf.data_ptr(), buf.numel(), out.data_ptr(), None, 0) == 0
+    outs = (VP * 4)()
+    outs[function] = multi.data_ptr()
+    assert lib.dgs_volume_forward_multi(mask, P, N, 1, *ptr, buf.data_ptr(), buf.numel(), outs, None, 0) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all() and torch.equal(multi, out)
+
+    dL = torch.randn((N, K), generator=torch.Generator().manual_seed(function)).to(dev)
+    ws = lib.dgs_volume_workspace_size(function, P, N, 1, 1)
+    assert ws == lib.dgs_volume_workspace_size_multi(mask, P, N, 1, 1) > 0
+    work = torch.empty(ws, dtype=torch.uint8, device=dev)
+    single = [torch.full(shape, nan, device=dev) for shape in ((P, 3), (P, 1), (P, 6))]
+    fused = [torch.full_like(g, nan) for g in single]
+    assert lib.dgs_volume_backward(function, P, N, 1, *ptr, dL.data_ptr(), buf.data_ptr(), buf.numel(),
+                                   *(g.data_ptr() for g in single), work.data_ptr(), ws, None, 0) == 0
+    dls = (VP * 4)()
+    dls[function] = dL.data_ptr()
+    assert lib.dgs_volume_backward_multi(mask, P, N, 1, *ptr, dls, buf.data_ptr(), buf.numel(),
+                                         *(g.data_ptr() for g in fused), work.data_ptr(), ws, None, 0) == 0
+    torch.cuda.synchronize()
+    for name, a, b in zip(("dmeans", "dvalues", "dconics"), fused, single):
+        assert torch.isfinite(b).all() and torch.equal(a, b), name
+
+
 def test_volume_grid_lattice(dgs):
     """A regular lattice of query points (the "256^3 grid" of BASELINE config 5, at 24^3)."""
     ax = np.arange(24, dtype=np.float64) * (2.0 / 24) - 1.0

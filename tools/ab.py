@@ -43,5 +43,7 @@ for r in range(a.rounds):
         res[v].append(j)
         print(r, v, json.dumps(j), flush=True)
 for v, js in res.items():
-    med = {k: statistics.median(j[k] for j in js) for k in ("fwd_ms", "bwd_ms", "call_pair_ms", "prep_ms", "separate_ms") if k in js[0]}
+    med = {k: statistics.median(j[k] for j in js) for k in ("fwd_ms", "bwd_ms", "call_pair_ms", "prep_ms", "fused_ms", "separate_ms") if k in js[0]}
+    for f in js[0].get("single_ms", {}):  # tools/volume_multi_bench.py: the per-function steps
+        med["single_ms." + f] = statistics.median(j["single_ms"][f] for j in js)
     print("MEDIAN", v, json.dumps(med), flush=True)

@@ -1,7 +1,7 @@
 """Times the fused D = 3 multi-function call against the per-function calls on one binning.
 
     python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
-                                       [--rounds 3] [--steps 3] [--separate-only]
+                                       [--rounds 3] [--steps 3] [--separate-only [--C 3]]
 
 The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice, C = 1).  After settle
 steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
@@ -10,7 +10,8 @@ backward step (preprocess excluded).  Prints one JSON line: fused_ms, separate_m
 per-function calls, same outputs and gradients), per-function step times `single_ms`, the speedup,
 and `fused_over_last`, the fused step against the most expensive (last named) function alone.
 --separate-only times the per-function calls only (a package without the fused call, for A/B
-runs through tools/ab.py --script).
+runs through tools/ab.py --script); --C sets the channel count of those calls (the fused call
+covers C = 1 only, so --C needs --separate-only).
 """
 import argparse
 import json
@@ -37,10 +38,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--settle", type=int, default=2)
     ap.add_argument("--separate-only", action="store_true")
+    ap.add_argument("--C", type=int, default=1, help="channels (other than 1: only with --separate-only)")
     args = ap.parse_args()
+    if args.C != 1 and not args.separate_only:
+        ap.error("--C other than 1 needs --separate-only (the fused call covers C = 1)")
+    C = args.C
     fns = args.functions.split(",")
     dev = torch.device("cuda:0")
-    means, values, covs, conics = (t.to(dev) for t in syn.gaussians3(args.P, 1, seed=0))
+    means, values, covs, conics = (t.to(dev) for t in syn.gaussians3(args.P, C, seed=0))
     samples = syn.grid_samples3(args.grid3).to(dev)
     N = samples.shape[0]
     for t in (means, values, conics):
@@ -48,7 +53,7 @@ def main():
     vs = VolumeSampler(False)
     vs.preprocess(means, values, covs, conics, samples)
     gen = torch.Generator().manual_seed(5)
-    w = {f: torch.randn((N,) + (3,) * FUNCTION_CODES[f] + (1,), generator=gen).to(dev) for f in fns}
+    w = {f: torch.randn((N,) + (3,) * FUNCTION_CODES[f] + (C,), generator=gen).to(dev) for f in fns}
     single = {"gaussian": vs.sample_gaussians, "derivative": vs.sample_gaussians_derivative,
               "laplacian": vs.sample_gaussians_laplacian, "third": vs.sample_gaussians_third_derivative}
 
@@ -79,7 +84,7 @@ def main():
         for k in kinds + fns:
             times[k].append(timed(k))
     med = {k: statistics.median(v) for k, v in times.items()}
-    res = {"P": args.P, "N": N, "grid3": args.grid3, "functions": fns, "rounds": args.rounds, "steps": args.steps,
+    res = {"P": args.P, "N": N, "C": C, "grid3": args.grid3, "functions": fns, "rounds": args.rounds, "steps": args.steps,
            "separate_ms": med["separate"], "single_ms": {f: med[f] for f in fns},
            "separate_rounds_ms": times["separate"]}
     if not args.separate_only:
