@@ -19,6 +19,8 @@
 //   * forward: lane = sample (in cell order), outputs summed in registers, no atomics;
 //     backward: lane = Gaussian (in cell order) walking the samples of its images, gradients
 //     in registers, no atomics; big Gaussians: one block each over every sample;
+//   * gradient of the samples (k_vol_sgrad_m<MASK>, k_vol_sgrad<FN, CB>): the
+//     forward's walk, lane = sample with its dL rows in registers, three sums per lane, no atomics;
 //   * the forward's loop nest is written once (walk_candidates) and called with two callables by
 //     k_vol_forward<FN, CB> at C > 1 and k_vol_forward_m<MASK> at C = 1, where a single function
 //     is the single-bit mask; the backward kernels (k_vol_backward<FN, CB>, k_vol_backward_m<MASK>
@@ -1344,6 +1346,175 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
     }
 }
 
+// ------------------------------------------------------------------------------ sample gradients
+// dL/d samples (DESIGN.md 4.9, D = 3): per pair dL/ds = v G (phi a - A g) = -dL/dm, with phi and
+// g = d phi / d a of phi_ge_t from the sample's tensor H.  The forward's walk (lane = sample,
+// walk_candidates, then the big Gaussians), so the pair set is the forward's; the lane reads its
+// own dL rows once, keeps H in registers, sums three values in a fixed order and stores them once.
+// No atomics, no cross-lane sums, no workspace.
+
+// the lane's H of function FN (k_vol_hsum's sums in its order, scaled as stage_h does)
+template <int FN>
+__device__ __forceinline__ void sg_load_h(const float *__restrict__ dL, int64_t sid, float *H) {
+    constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    float h[KU];
+    for (int u = 0; u < KU; ++u) h[u] = 0.0f;
+#pragma unroll
+    for (int f = 0; f < K; ++f) h[umap<FN>(f)] += dL[sid * K + f];
+    for (int u = 0; u < KU; ++u) H[u] = h[u] * vol_inv_mult<FN>(u);
+}
+// ds += w (phi a - A g), w = v G
+__device__ __forceinline__ void sg_add(float w, float phi, const float *a, const float *c, const float *g,
+                                       float *ds) {
+    const float Ag[3] = {c[0] * g[0] + c[1] * g[1] + c[2] * g[2], c[1] * g[0] + c[3] * g[1] + c[4] * g[2],
+                         c[2] * g[0] + c[4] * g[1] + c[5] * g[2]};
+    for (int d = 0; d < 3; ++d) ds[d] += w * (phi * a[d] - Ag[d]);
+}
+
+struct VDLs {
+    const float *p[4];  // dL/d out per function code; entries outside the mask unused
+};
+
+// C = 1, every mask
+template <int MASK>
+__global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ buf, int P, int N,
+                                                       const float *__restrict__ means,
+                                                       const float *__restrict__ values,
+                                                       const float *__restrict__ conics,
+                                                       const float *__restrict__ samples, VDLs dLs,
+                                                       float *__restrict__ dsamples) {
+    constexpr int SKU = mask_ku(MASK);
+    constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    __shared__ VCand<1> cand[kWave];
+    const Hdr &h = hdr_of(buf);
+    const int lane = threadIdx.x;
+    if (vol_stale(buf, h, P, N)) {  // stale buffer / inputs: loud
+        for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < (int64_t)N * 3; i += (int64_t)gridDim.x * kWave)
+            dsamples[i] = NAN;
+        return;
+    }
+    const Bin bin = bin_of(buf, h);
+    for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
+        const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
+        for (int j0 = sb; j0 < se; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool active = j < se;
+            const int sid = active ? bin.sids[j] : 0;
+            float s[3], H[SKU];
+            for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
+            for (int u = 0; u < SKU; ++u) H[u] = 0.0f;
+            if (active) {
+                if constexpr ((MASK & 1) != 0) sg_load_h<0>(dLs.p[0], sid, H + O0);
+                if constexpr ((MASK & 2) != 0) sg_load_h<1>(dLs.p[1], sid, H + O1);
+                if constexpr ((MASK & 4) != 0) sg_load_h<2>(dLs.p[2], sid, H + O2);
+                if constexpr ((MASK & 8) != 0) sg_load_h<3>(dLs.p[3], sid, H + O3);
+            }
+            float ds[3] = {0.0f, 0.0f, 0.0f};
+            auto eval = [&](const float *m, const float *c, float v) {
+                float X[3], a[3], G;
+                if (!pair_eval(m, s, c, X, G, a)) return;
+                const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
+                float phi = 0.0f, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
+                if constexpr ((MASK & 1) != 0) phi_ge_add<0>(H + O0, a, c2, phi, g, e);
+                if constexpr ((MASK & 2) != 0) phi_ge_add<1>(H + O1, a, c2, phi, g, e);
+                if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, g, e);
+                if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, g, e);
+                sg_add(v * G, phi, a, c, g, ds);
+            };
+            walk_candidates<1>(
+                h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
+                [&](const float *m, const float *c, const float *vr) { eval(m, c, vr[0]); });
+            if (active) {
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
+                    float m[3], c[6];
+                    for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+                    for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                    eval(m, c, values[g]);
+                }
+                for (int d = 0; d < 3; ++d) dsamples[(int64_t)sid * 3 + d] = ds[d];
+            }
+        }
+    }
+}
+
+// C > 1, one function, CB channels per launch: hv_u = sum_ch v_ch h_u,ch over the block's channels
+// per pair; the launches after the first (cbase > 0) add onto the owning lane's stored row.
+template <int FN, int CB>
+__global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ buf, int P, int N, int C, int cbase,
+                                                     const float *__restrict__ means,
+                                                     const float *__restrict__ values,
+                                                     const float *__restrict__ conics,
+                                                     const float *__restrict__ samples,
+                                                     const float *__restrict__ dL, float *__restrict__ dsamples) {
+    constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    __shared__ VCand<CB> cand[kWave];
+    const Hdr &h = hdr_of(buf);
+    const int lane = threadIdx.x;
+    const int nch = min(CB, C - cbase);
+    if (vol_stale(buf, h, P, N)) {
+        for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < (int64_t)N * 3; i += (int64_t)gridDim.x * kWave)
+            dsamples[i] = NAN;
+        return;
+    }
+    const Bin bin = bin_of(buf, h);
+    for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
+        const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
+        for (int j0 = sb; j0 < se; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool active = j < se;
+            const int sid = active ? bin.sids[j] : 0;
+            float s[3];
+            for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
+            float hh[KU][CB];  // the tensor H per channel of the block
+            for (int u = 0; u < KU; ++u)
+                for (int ch = 0; ch < CB; ++ch) hh[u][ch] = 0.0f;
+            if (active) {
+#pragma unroll
+                for (int f = 0; f < K; ++f)
+                    for (int ch = 0; ch < CB; ++ch)
+                        if (ch < nch) hh[umap<FN>(f)][ch] += dL[((int64_t)sid * K + f) * C + cbase + ch];
+                for (int u = 0; u < KU; ++u)
+                    for (int ch = 0; ch < CB; ++ch) hh[u][ch] *= vol_inv_mult<FN>(u);
+            }
+            float ds[3] = {0.0f, 0.0f, 0.0f};
+            auto values_of = [&](float *vr, int g) {
+                for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
+            };
+            auto eval = [&](const float *m, const float *c, const float *vr) {
+                float X[3], a[3], G;
+                if (!pair_eval(m, s, c, X, G, a)) return;
+                float hv[KU];
+                for (int u = 0; u < KU; ++u) {
+                    hv[u] = 0.0f;
+                    for (int ch = 0; ch < CB; ++ch) hv[u] += vr[ch] * hh[u][ch];
+                }
+                const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
+                float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
+                phi_ge_t<FN>(hv, a, c2, phi, g, e);
+                sg_add(G, phi, a, c, g, ds);
+            };
+            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            if (active) {
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
+                    float m[3], c[6], vr[CB];
+                    for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+                    for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                    values_of(vr, g);
+                    eval(m, c, vr);
+                }
+                for (int d = 0; d < 3; ++d) {
+                    float *o = dsamples + (int64_t)sid * 3 + d;
+                    *o = cbase == 0 ? ds[d] : *o + ds[d];
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ launches
 struct VArgs {  // what every launch takes
     const char *buf;
@@ -1394,6 +1565,20 @@ static void launch_bwd(const VArgs &a, const float *dL, float *hs, float *dm, fl
         k_vol_backward_big<FN, CB><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
                                                             a.samples, hs, dm, dv, dc);
     }
+}
+
+// sample gradients: every mask at C = 1; one function, 4 (C <= 4) or 8 channels per launch
+template <int MASK>
+static void launch_sgrad_m(const VArgs &a, const float *const *dLs, float *ds) {
+    VDLs d;
+    for (int f = 0; f < 4; ++f) d.p[f] = (MASK >> f) & 1 ? dLs[f] : nullptr;
+    k_vol_sgrad_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, d, ds);
+}
+template <int FN, int CB>
+static void launch_sgrad(const VArgs &a, const float *dL, float *ds) {
+    for (int cb = 0; cb < a.C; cb += CB)
+        k_vol_sgrad<FN, CB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
+                                                              a.samples, dL, ds);
 }
 
 // the masks of the forward kernels (all 15) and of the fused backward (two or more functions)
@@ -1665,6 +1850,48 @@ extern "C" int dgs_volume_backward_multi(int mask, int P, int N, int C, const fl
                                          size_t workspace_bytes, dgs_stream_t stream, int debug) {
     return vol_backward(true, mask, P, N, C, means, values, conics, samples, dL_douts, binning, binning_bytes, dL_dmeans,
                         dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
+}
+
+// The lanes keep their dL rows in registers: no workspace (the function exists so that callers
+// size it the way they size the other calls').
+extern "C" size_t dgs_volume_sample_grad_workspace_size(int mask, int P, int N, int C) { return 0; }
+
+extern "C" int dgs_volume_backward_samples(int mask, int P, int N, int C, const float *means, const float *values,
+                                           const float *conics, const float *samples, const float *const *dL_douts,
+                                           const void *binning, size_t binning_bytes, float *dL_dsamples,
+                                           void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    if (int rc = vol_check(true, mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples: dL_douts required");
+    if (N == 0) return DGS_OK;
+    if (!dL_dsamples) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples: dL_dsamples required");
+    for (int f = 0; f < 4; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_samples: a dL_dout of the mask is NULL");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dsamples, 0, (size_t)N * 12, s));
+        return DGS_OK;
+    }
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {  // every mask, a single function included
+        switch (mask) {
+#define X(M) case M: launch_sgrad_m<M>(a, dL_douts, dL_dsamples); break;
+            DGS_VOL_MASKS(X)
+#undef X
+        }
+    } else {  // (vol_check: a single function)
+        // The lane holds KU x CB floats of H next to the walk's registers.  The forward's blocks (4 for
+        // C <= 4, else 8) fit up to the laplacian (6 x 8); the third's 10 x 8 would spill, so it always
+        // takes 4 channels per launch (10 x 4: no scratch).
+        switch (mask_top(mask) == 3 ? DGS_VOL_FN_CB_CASE(3, 4) : fn_cb_case(mask, C)) {
+#define X(FN, CB) case DGS_VOL_FN_CB_CASE(FN, CB): launch_sgrad<FN, CB>(a, dL_douts[FN], dL_dsamples); break;
+            X(0, 4) X(0, 8) X(1, 4) X(1, 8) X(2, 4) X(2, 8) X(3, 4)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
 }
 
 extern "C" int dgs_volume_count_pairs(int P, int N, const float *means, const float *conics, const float *samples,

@@ -1156,6 +1156,58 @@ std::tuple<Tensor, Tensor, Tensor> VolumeBackwardMulti(const std::vector<int64_t
     return std::make_tuple(dm, dv, dc);
 }
 
+// dL / d samples at D = 3 (dgs_volume_backward_samples): [N, 3].  Several codes at C = 1 share one
+// walk; at C > 1 (which the C entry refuses for several) the single-function calls run in turn and
+// their results are added, as VolumeBackwardMulti's fallback does.
+Tensor VolumeSamplesBackward(const std::vector<int64_t> &codes, const Tensor &means_in, const Tensor &values_in,
+                             const Tensor &conics_in, const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
+                             const Tensor &binning_in, const bool debug) {
+    const int mask = function_mask(codes);
+    TORCH_CHECK(dLs_in.size() == codes.size(), "one dL_dout per sampling function");
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    std::vector<Tensor> dLs;
+    for (size_t i = 0; i < codes.size(); ++i) {
+        int64_t K = 1;
+        for (int k = 0; k < (int)codes[i]; ++k) K *= 3;
+        dLs.push_back(f32(dLs_in[i], "dL_dout"));
+        TORCH_CHECK(dLs.back().numel() == N * K * C, "volume: dL_dout must be [N, 3^function, C]");
+    }
+    Tensor ds = torch::zeros({N, 3}, means.options());
+    if (N == 0 || P == 0 || C == 0) return ds;
+    auto call = [&](int m, const float *const *ptr, Tensor &out) {
+        const size_t ws = dgs_volume_sample_grad_workspace_size(m, (int)P, (int)N, (int)C);
+        Tensor work = torch::empty({(int64_t)std::max<size_t>(ws, 4)}, means.options().dtype(torch::kUInt8));
+        check(dgs_volume_backward_samples(m, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+                                          conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(),
+                                          (size_t)binning.numel(), out.data_ptr<float>(), work.data_ptr(), ws,
+                                          as_dgs(cur_stream()), debug ? 1 : 0),
+              "volume_samples_backward");
+    };
+    if (codes.size() == 1 || C == 1) {
+        const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (size_t i = 0; i < codes.size(); ++i) ptr[codes[i]] = dLs[i].data_ptr<float>();
+        call(mask, ptr, ds);
+        return ds;
+    }
+    for (size_t i = 0; i < codes.size(); ++i) {
+        const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        ptr[codes[i]] = dLs[i].data_ptr<float>();
+        if (i == 0) {
+            call(1 << codes[i], ptr, ds);
+        } else {
+            Tensor part = torch::empty({N, 3}, means.options());
+            call(1 << codes[i], ptr, part);
+            ds.add_(part);
+        }
+    }
+    return ds;
+}
+
 std::tuple<int64_t, int64_t> VolumeCountPairs(const Tensor &means_in, const Tensor &conics_in,
                                               const Tensor &samples_in, const Tensor &binning_in) {
     const Tensor means = f32(means_in, "means"), conics = f32(conics_in, "conics");
@@ -1214,6 +1266,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("volume_backward", &VolumeBackward);
     m.def("volume_forward_multi", &VolumeForwardMulti);
     m.def("volume_backward_multi", &VolumeBackwardMulti);
+    m.def("volume_samples_backward", &VolumeSamplesBackward);
     m.def("volume_count_pairs", &VolumeCountPairs);
     m.def("library_version", []() { return dgs_version(); });
     m.def("warmup", []() { check(dgs_warmup(as_dgs(cur_stream())), "warmup"); });

@@ -14,6 +14,16 @@ truncation; only pairs whose contribution is exactly 0 in fp32 are skipped).
 Outputs are [N, 3, ..., 3, C] (3^k components for the k-th derivative), gradients flow to
 means [P, 3], values [P, C] and conics [P, 6] through autograd, as in the reference's
 Functions (diff_gaussian_sampling/__init__.py:80-160 of the reference).
+
+The gradient with respect to the sample positions [N, 3] (moving or learned collocation points,
+advected tracers, a learned warp in front of the sampler) is opt-in:
+`VolumeSampler(debug, sample_grad=True)`, or `sample_grad=True` on `sample_volume` /
+`sample_volume_multi`.  It costs a third walk of the candidates, about a forward's time, on top
+of the forward and the backward, and nobody should pay that because a tensor happens to carry
+requires_grad: without the flag, samples that require a gradient raise NotImplementedError as
+before.  With it, `samples.grad` is filled (the pair set held fixed, the wrap with slope 1, as
+for the other gradients), and the gradients of means, values and conics are bit for bit what they
+are without it.
 """
 import torch
 
@@ -31,7 +41,8 @@ class _SampleVolume(torch.autograd.Function):
     @staticmethod
     def forward(ctx, function, means, values, conics, samples, binning, debug):
         if ctx.needs_input_grad[4]:  # (the sample-position gradient is D = 1 / 2 only: DESIGN.md 4.9)
-            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them")
+            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them "
+                                      "(or ask for it: sample_grad=True)")
         out = call_debug(_C.volume_forward, debug, "vol_fw", function, means, values, conics, samples,
                          binning, debug)
         ctx.function, ctx.debug = function, debug
@@ -46,18 +57,48 @@ class _SampleVolume(torch.autograd.Function):
         return None, gm, gv, gc, None, None, None
 
 
-def sample_volume(function, means, values, conics, samples, binning, debug=False):
+class _SampleVolumeSG(torch.autograd.Function):
+    """_SampleVolume with the sample-position gradient (sample_grad=True): the same _C calls for
+    the output and the parameters' gradients, plus _C.volume_samples_backward when samples need one."""
+
+    @staticmethod
+    def forward(ctx, function, means, values, conics, samples, binning, debug):
+        out = call_debug(_C.volume_forward, debug, "vol_fw", function, means, values, conics, samples,
+                         binning, debug)
+        ctx.function, ctx.debug = function, debug
+        ctx.save_for_backward(means, values, conics, samples, binning)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        means, values, conics, samples, binning = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        gm = gv = gc = gs = None
+        if any(ctx.needs_input_grad[1:4]):
+            gm, gv, gc = call_debug(_C.volume_backward, ctx.debug, "vol_bw", ctx.function, means, values,
+                                    conics, samples, binning, grad_out, ctx.debug)
+        if ctx.needs_input_grad[4]:
+            gs = call_debug(_C.volume_samples_backward, ctx.debug, "vol_sg", [ctx.function], means, values,
+                            conics, samples, [grad_out], binning, ctx.debug)
+        return None, gm, gv, gc, gs, None, None
+
+
+def sample_volume(function, means, values, conics, samples, binning, debug=False, sample_grad=False):
     """One of the four functions ("gaussian", "derivative", "laplacian", "third" or 0..3) of a
-    D = 3 field at `samples`, through the binning of preprocess_volume."""
+    D = 3 field at `samples`, through the binning of preprocess_volume.  sample_grad=True also
+    returns the gradient of `samples` when they require one (one more walk of the candidates, about
+    a forward's time; without the flag such samples raise NotImplementedError)."""
     code = FUNCTION_CODES[function] if isinstance(function, str) else int(function)
-    return _SampleVolume.apply(code, means, values, conics, samples, binning, debug)
+    fn = _SampleVolumeSG if sample_grad else _SampleVolume
+    return fn.apply(code, means, values, conics, samples, binning, debug)
 
 
 class _SampleVolumeMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, codes, means, values, conics, samples, binning, debug):
         if ctx.needs_input_grad[4]:
-            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them")
+            raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them "
+                                      "(or ask for it: sample_grad=True)")
         outs = call_debug(_C.volume_forward_multi, debug, "vol_multi_fw", list(codes), means, values, conics,
                           samples, binning, debug)
         ctx.codes, ctx.debug = codes, debug
@@ -75,13 +116,44 @@ class _SampleVolumeMulti(torch.autograd.Function):
         return None, gm, gv, gc, None, None, None
 
 
-def sample_volume_multi(functions, means, values, conics, samples, binning, debug=False):
+class _SampleVolumeMultiSG(torch.autograd.Function):
+    """_SampleVolumeMulti with the sample-position gradient (sample_grad=True), over the live
+    outputs only."""
+
+    @staticmethod
+    def forward(ctx, codes, means, values, conics, samples, binning, debug):
+        outs = call_debug(_C.volume_forward_multi, debug, "vol_multi_fw", list(codes), means, values, conics,
+                          samples, binning, debug)
+        ctx.codes, ctx.debug = codes, debug
+        ctx.save_for_backward(means, values, conics, samples, binning)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        means, values, conics, samples, binning = ctx.saved_tensors
+        live = [(c, g.contiguous()) for c, g in zip(ctx.codes, grads) if g is not None]
+        if not live:
+            return (None,) * 7
+        gm = gv = gc = gs = None
+        if any(ctx.needs_input_grad[1:4]):
+            gm, gv, gc = call_debug(_C.volume_backward_multi, ctx.debug, "vol_multi_bw", [c for c, _ in live],
+                                    means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
+        if ctx.needs_input_grad[4]:
+            gs = call_debug(_C.volume_samples_backward, ctx.debug, "vol_multi_sg", [c for c, _ in live], means,
+                            values, conics, samples, [g for _, g in live], binning, ctx.debug)
+        return None, gm, gv, gc, gs, None, None
+
+
+def sample_volume_multi(functions, means, values, conics, samples, binning, debug=False, sample_grad=False):
     """Several of the four functions (distinct names or codes) of a D = 3 field at `samples`;
     returns their outputs in the order asked.  At C = 1 they share one walk of the candidates,
     forward and backward (include/dgs_volume.h, dgs_volume_*_multi); each output is bitwise the
-    one `sample_volume` returns.  An output whose gradient is None is left out of the backward."""
+    one `sample_volume` returns.  An output whose gradient is None is left out of the backward.
+    sample_grad=True: as for `sample_volume`, the gradient of `samples` over the live outputs (one
+    walk at C = 1, the per-function calls added at C > 1)."""
     codes = tuple(FUNCTION_CODES[f] if isinstance(f, str) else int(f) for f in functions)
-    return _SampleVolumeMulti.apply(codes, means, values, conics, samples, binning, debug)
+    fn = _SampleVolumeMultiSG if sample_grad else _SampleVolumeMulti
+    return fn.apply(codes, means, values, conics, samples, binning, debug)
 
 
 class VolumeSampler:
@@ -91,10 +163,17 @@ class VolumeSampler:
     the conics.  The tensors are kept by reference: when means, conics or samples were changed
     in place since preprocess (an optimizer step), the next sampling call re-bins them first.
     (The functional `sample_volume` with a stale binning writes NaN instead: every call compares
-    its tensors with the binned ones on the device, include/dgs_volume.h.)"""
+    its tensors with the binned ones on the device, include/dgs_volume.h.)
 
-    def __init__(self, debug=False):
+    sample_grad=True fills `samples.grad` too when the samples require a gradient:
+    one more walk of the candidates per backward, about a forward's time, which is why it is asked
+    for and not inferred from requires_grad; the default raises NotImplementedError for such
+    samples.  Samples stepped in place (`samples -= lr * samples.grad` under no_grad) are re-binned
+    by the next call like any other changed tensor."""
+
+    def __init__(self, debug=False, sample_grad=False):
         self.debug = debug
+        self.sample_grad = sample_grad
 
     def preprocess(self, means, values, covariances, conics, samples):
         self.binning = preprocess_volume(means, conics, samples, self.debug)
@@ -120,14 +199,14 @@ class VolumeSampler:
     def _run(self, code):
         self._rebin_if_changed()
         return sample_volume(code, self.means, self.values, self.conics, self.samples, self.binning,
-                             self.debug)
+                             self.debug, self.sample_grad)
 
     def sample_gaussians_multi(self, *functions):
         """Several functions ("gaussian", "derivative", "laplacian", "third" or 0..3) in one
         call; returns a tuple in the order asked (sample_volume_multi)."""
         self._rebin_if_changed()
         return sample_volume_multi(functions, self.means, self.values, self.conics, self.samples,
-                                   self.binning, self.debug)
+                                   self.binning, self.debug, self.sample_grad)
 
     def sample_gaussians(self):
         return self._run(0)

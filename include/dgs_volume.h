@@ -86,6 +86,24 @@ int dgs_volume_backward_multi(int mask, int P, int N, int C, const float *means,
                               float *dL_dvalues, float *dL_dconics, void *workspace,
                               size_t workspace_bytes, dgs_stream_t stream, int debug);
 
+/* Gradient with respect to the sample positions (DESIGN.md §4.9, D = 3).  `mask` and dL_douts are
+ * those of dgs_volume_backward_multi (a single function f is the mask 1 << f, any C; two or more
+ * functions need C = 1, DGS_ERR_ARG otherwise).  Writes (overwrites) dL_dsamples[N][3]:
+ *   dL/ds_n = sum_g G (phi a - A g),  phi = sum_u hv_u t_u,  g = d phi / d a,
+ *   hv_u = sum_ch v_ch h_u,ch,  h = dL summed over the full components of unique component u,
+ * summed over the forward's pair set (the pair set held fixed, the wrap with slope 1); per pair it
+ * is minus that pair's share of dL_dmeans, so sum_n dL/ds_n = -sum_p dL/dm_p.  One walk of the
+ * candidates, lane = sample, no atomics (repeated calls are bit-identical).  Zeros for P = 0,
+ * nothing to do for N = 0; the stale buffer / changed input guard writes NaN to every entry.  No
+ * host sync, no allocation; calls on one binning are ordered as the others are.  The workspace
+ * size is 0 today (workspace may be NULL); callers size it through the function all the same.
+ * New exported functions only: DGS_ABI_VERSION is unchanged (dgs.h, on the D = 2 pair). */
+size_t dgs_volume_sample_grad_workspace_size(int mask, int P, int N, int C);
+int dgs_volume_backward_samples(int mask, int P, int N, int C, const float *means, const float *values,
+                                const float *conics, const float *samples, const float *const *dL_douts,
+                                const void *binning, size_t binning_bytes, float *dL_dsamples,
+                                void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
+
 /* Diagnostic (not on any reference API): counts[0] = pairs the forward evaluates (candidates
  * inside their own cut box), counts[1] = live pairs (G = expf(power) > 0).  Host, syncs;
  * DGS_ERR_BUFFER when the inputs differ from the binned ones. */
