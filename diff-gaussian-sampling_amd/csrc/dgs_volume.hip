@@ -26,6 +26,9 @@
 //     is the single-bit mask; the backward kernels (k_vol_backward<FN, CB>, k_vol_backward_m<MASK>
 //     for two or more functions) each hold the lane = Gaussian nest: their pair arithmetic is
 //     contracted by the compiler, and its last bits move when the nest does.
+//   * several functions of a field of 2..4 channels: the _mc kernels ("mask, channels", below the
+//     sample gradients), one walk for every function and channel in the forward, the backward
+//     (moment form, its own loop nest walk_samples) and the sample gradient.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1515,6 +1518,412 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ bu
     }
 }
 
+// ------------------------------------------------------------------------------ C = 2..4: function masks
+// Two or more of the four functions of one field of 2 <= C <= 4 channels at the same samples
+// ("fused functions at C = 2..4"): one walk of the candidates and one pair_eval per
+// kept pair for every function of MASK and every channel of the one block of CB = 4; the suffix
+// _mc is "mask, channels".  Channels >= C of the block are selected to 0 and never loaded or stored.
+template <int MASK, class F>
+__host__ __device__ __forceinline__ void for_mask(F f) {  // f(integral_constant<int, FN>) per function of MASK
+    if constexpr ((MASK & 1) != 0) f(std::integral_constant<int, 0>{});
+    if constexpr ((MASK & 2) != 0) f(std::integral_constant<int, 1>{});
+    if constexpr ((MASK & 4) != 0) f(std::integral_constant<int, 2>{});
+    if constexpr ((MASK & 8) != 0) f(std::integral_constant<int, 3>{});
+}
+
+// acc[u][ch] += v_ch G t_u for function FN with every rounding written out, so that an output does
+// not depend on the other functions of the mask: fma(v, G, acc) for the gaussian and
+// fma(round(v G), t_u, acc) for the others, among the staged candidates and the big Gaussians
+// alike.  These are the roundings the compiler gives k_vol_forward<FN, 4>.
+template <int FN, int CB>
+__device__ __forceinline__ void fwd_acc_c(int nch, const float *vr, float G, const float *a, const float *c,
+                                          float (*acc)[CB]) {
+    constexpr int KU = VTr<FN>::KU;
+    float t[KU];
+    terms<FN>(a, c, t);
+#pragma unroll
+    for (int ch = 0; ch < CB; ++ch) {
+        if (ch >= nch) continue;
+        if constexpr (FN == 0) {
+            acc[0][ch] = __builtin_fmaf(vr[ch], G, acc[0][ch]);
+        } else {
+            const float vG = rmul(vr[ch], G);
+#pragma unroll
+            for (int u = 0; u < KU; ++u) acc[u][ch] = __builtin_fmaf(vG, t[u], acc[u][ch]);
+        }
+    }
+}
+
+template <int MASK, int CB>
+__global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict__ buf, int P, int N, int C,
+                                                          const float *__restrict__ means,
+                                                          const float *__restrict__ values,
+                                                          const float *__restrict__ conics,
+                                                          const float *__restrict__ samples, VOuts outs) {
+    constexpr int SKU = mask_ku(MASK);
+    __shared__ VCand<CB> cand[kWave];
+    const Hdr &h = hdr_of(buf);
+    const int lane = threadIdx.x;
+    const int nch = min(CB, C);
+    if (vol_stale(buf, h, P, N)) {
+        for (int64_t j = (int64_t)blockIdx.x * kWave + lane; j < N; j += (int64_t)gridDim.x * kWave)
+            for_mask<MASK>([&](auto fc) {
+                constexpr int FN = decltype(fc)::value, K = VTr<FN>::K;
+                for (int f = 0; f < K; ++f)
+                    for (int ch = 0; ch < nch; ++ch) outs.p[FN][(j * K + f) * C + ch] = NAN;
+            });
+        return;
+    }
+    const Bin bin = bin_of(buf, h);
+    for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
+        const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
+        for (int j0 = sb; j0 < se; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool active = j < se;
+            const int sid = active ? bin.sids[j] : 0;
+            float s[3];
+            for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
+            float acc[SKU][CB];
+            for (int u = 0; u < SKU; ++u)
+                for (int ch = 0; ch < CB; ++ch) acc[u][ch] = 0.0f;
+            auto values_of = [&](float *vr, int g) {
+                for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + ch] : 0.0f;
+            };
+            auto eval = [&](const float *m, const float *c, const float *vr) {
+                float X[3], a[3], G;
+                if (!pair_eval(m, s, c, X, G, a)) return;
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value;
+                    fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc + mask_off(MASK, FN));
+                });
+            };
+            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            if (active) {
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
+                    float m[3], c[6], vr[CB];
+                    for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+                    for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                    values_of(vr, g);
+                    eval(m, c, vr);
+                }
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value, K = VTr<FN>::K, O = mask_off(MASK, FN);
+                    float *__restrict__ out = outs.p[FN];
+#pragma unroll
+                    for (int f = 0; f < K; ++f)
+#pragma unroll
+                        for (int ch = 0; ch < CB; ++ch)
+                            if (ch < nch) out[((int64_t)sid * K + f) * C + ch] = acc[O + umap<FN>(f)][ch];
+                });
+            }
+        }
+    }
+}
+
+// k_vol_hsum into function FN's slice of the concatenated rows hs[N][sum KU][C]: the slice sits at
+// off = mask_off(mask, FN) * C of a row of stride = mask_ku(mask) * C floats, in k_vol_hsum's
+// [KU][C] layout (bwd_pair<FN, 4> reads it unchanged).
+template <int FN>
+__global__ __launch_bounds__(kBlock) void k_vol_hsum_cat_c(int N, int C, const float *__restrict__ dL,
+                                                           float *__restrict__ hs, int stride, int off) {
+    constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (int64_t)N * C) return;
+    const int64_t sid = t / C;
+    const int ch = (int)(t - sid * C);
+    float h[KU];
+    for (int u = 0; u < KU; ++u) h[u] = 0.0f;
+#pragma unroll
+    for (int f = 0; f < K; ++f) h[umap<FN>(f)] += dL[(sid * K + f) * C + ch];
+    for (int u = 0; u < KU; ++u) hs[sid * stride + off + u * C + ch] = h[u];
+}
+
+// The lane = Gaussian loop nest of the backward, for k_vol_backward_mc alone (k_vol_backward and
+// k_vol_backward_m keep their own copies: their contracted pair arithmetic moves with the nest,
+// DESIGN.md 4.8).  The wave's Gaussians (mean m, cut half-widths r, `active` lanes) walk the image
+// windows of their union; the samples of a row of cells are staged 64 at a time: stage(slot, sid)
+// fills what the kernel keeps per staged sample, eval(slot, sv) takes a sample inside the lane's
+// own cut box.
+template <class Stage, class Eval>
+__device__ __forceinline__ void walk_samples(const Hdr &h, const int32_t *__restrict__ sids,
+                                             const int32_t *__restrict__ sstart, const float *__restrict__ samples,
+                                             float4 *scand, int lane, bool active, const float *m, const float *r,
+                                             Stage stage, Eval eval) {
+    float ml[3], mh[3], R[3];
+    Win w[3];
+    for (int d = 0; d < 3; ++d) {
+        float mn = active ? m[d] : INFINITY, mx = active ? m[d] : -INFINITY, rr = r[d];
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, o));
+            mx = fmaxf(mx, __shfl_xor(mx, o));
+            rr = fmaxf(rr, __shfl_xor(rr, o));
+        }
+        ml[d] = mn; mh[d] = mx; R[d] = rr;
+        w[d] = box_images(h, d, mn, mx, rr, false);
+    }
+    for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
+        for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
+            for (int kx = w[0].k0; kx <= w[0].k1; ++kx) {
+                const int kk[3] = {kx, ky, kz};
+                int c0[3], c1[3];
+                bool any = true;
+                for (int d = 0; d < 3 && any; ++d)  // the sample window
+                    any = window_cells(h, d, kk[d], R[d], ml[d], mh[d], false, c0[d], c1[d]);
+                if (!any) continue;
+                for (int cz = c0[2]; cz <= c1[2]; ++cz)
+                    for (int cy = c0[1]; cy <= c1[1]; ++cy) {
+                        const int row = (cz * h.n[1] + cy) * h.n[0];
+                        const int b = sstart[row + c0[0]], e = sstart[row + c1[0] + 1];
+                        for (int q0 = b; q0 < e; q0 += kWave) {
+                            const int q = q0 + lane;
+                            __syncthreads();
+                            if (q < e) {
+                                const int sid = sids[q];
+                                scand[lane] = make_float4(samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1],
+                                                          samples[(int64_t)sid * 3 + 2], __int_as_float(sid));
+                                stage(lane, sid);
+                            }
+                            __syncthreads();
+                            const int cnt = min(kWave, e - q0);
+                            if (active)
+                                for (int u = 0; u < cnt; ++u) {
+                                    const float4 sp = scand[u];
+                                    const float sv[3] = {sp.x, sp.y, sp.z};
+                                    if (in_cut_box(m, sv, r, kk)) eval(u, sv);
+                                }
+                        }
+                    }
+            }
+}
+
+// The fused backward at C = 2..4 in the moment form (vol_mom_add / vol_mom_finish above): the lane
+// keeps its v[ch]; a staged sample carries its tensors H[ch][sum KU] (hs scaled by vol_inv_mult, one
+// column per channel, the columns >= C selected to 0).  Per kept pair hv_u = sum_ch v_ch H_ch,u, then
+// phi, g, e of hv over the mask's functions and one vol_mom_add; dv[ch] += G phi(H_ch).  v is inside
+// hv, so the rows are stored with scale 1.  No atomics, a fixed order of additions.
+template <int MASK, int CB>
+__global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restrict__ buf, int P, int N, int C,
+                                                           const float *__restrict__ means,
+                                                           const float *__restrict__ values,
+                                                           const float *__restrict__ conics,
+                                                           const float *__restrict__ samples,
+                                                           const float *__restrict__ hs, float *__restrict__ dmeans,
+                                                           float *__restrict__ dvalues, float *__restrict__ dconics) {
+    constexpr int SKU = mask_ku(MASK), TOP = mask_top(MASK);
+    __shared__ float4 scand[kWave];
+    __shared__ float shrow[kWave][CB][SKU];  // the candidates' H, channel after channel
+    const Hdr &h = hdr_of(buf);
+    const int lane = threadIdx.x;
+    const int nch = min(CB, C);
+    if (vol_stale(buf, h, P, N)) {  // stale buffer / inputs: loud
+        const float nan[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+        for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < P; i += (int64_t)gridDim.x * kWave)
+            bwd_store<CB>((int)i, C, 0, nch, nan, nan, nan, dmeans, dvalues, dconics);
+        return;
+    }
+    const Bin bin = bin_of(buf, h);
+    for (int cell = blockIdx.x; cell < 2 * h.ncells; cell += gridDim.x) {  // (class-major cells)
+        const int gb = bin.gstart[cell], ge = bin.gstart[cell + 1];
+        for (int i0 = gb; i0 < ge; i0 += kWave) {
+            const int i = i0 + lane;
+            const bool active = i < ge;
+            float m[3] = {0.0f, 0.0f, 0.0f}, r[3] = {0.0f, 0.0f, 0.0f}, c[6], v[CB];
+            int g = 0;
+            for (int k = 0; k < 6; ++k) c[k] = 0.0f;
+            for (int ch = 0; ch < CB; ++ch) v[ch] = 0.0f;
+            if (active) {
+                const float4 mp = bin.gpk[i], ex = bin.gek[i];
+                g = __float_as_int(mp.w);
+                m[0] = mp.x; m[1] = mp.y; m[2] = mp.z;
+                r[0] = ex.x; r[1] = ex.y; r[2] = ex.z;
+                for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                for (int ch = 0; ch < CB; ++ch)
+                    if (ch < nch) v[ch] = values[(int64_t)g * C + ch];
+            }
+            VMom mom{};
+            float dv[CB];
+            for (int ch = 0; ch < CB; ++ch) dv[ch] = 0.0f;
+            const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
+            auto stage = [&](int slot, int sid) {
+                const float *__restrict__ hrow = hs + (int64_t)sid * SKU * C;
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value, KU = VTr<FN>::KU, O = mask_off(MASK, FN);
+#pragma unroll
+                    for (int ch = 0; ch < CB; ++ch)
+#pragma unroll
+                        for (int u = 0; u < KU; ++u)
+                            shrow[slot][ch][O + u] = ch < nch ? hrow[(O + u) * C + ch] * vol_inv_mult<FN>(u) : 0.0f;
+                });
+            };
+            auto eval = [&](int slot, const float *sv) {
+                float X[3], a[3], G;
+                if (!pair_eval(m, sv, c, X, G, a)) return;
+                float hv[SKU];
+                for (int u = 0; u < SKU; ++u) hv[u] = 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < CB; ++ch) {
+                    if (ch >= nch) continue;
+                    const float *H = &shrow[slot][ch][0];
+                    float p = 0.0f, gd[3] = {0.0f, 0.0f, 0.0f}, ed[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (gd, ed unused)
+                    for_mask<MASK>([&](auto fc) {
+                        constexpr int FN = decltype(fc)::value;
+                        phi_ge_add<FN>(H + mask_off(MASK, FN), a, c2, p, gd, ed);
+                    });
+                    dv[ch] += G * p;
+#pragma unroll
+                    for (int u = 0; u < SKU; ++u) hv[u] += v[ch] * H[u];
+                }
+                float phi = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f}, ee[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value;
+                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, gg, ee);
+                });
+                vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
+            };
+            walk_samples(h, bin.sids, bin.sstart, samples, scand, lane, active, m, r, stage, eval);
+            float dm[3], dc[6], dphi[1];
+            vol_mom_finish(c, mom, dm, dc, dphi);
+            if (active) bwd_store<CB>(g, C, 0, nch, dm, dc, dv, dmeans, dvalues, dconics);
+        }
+    }
+}
+
+// Big Gaussians of the fused backward at C = 2..4: the per-function pair terms (bwd_pair<FN, CB> on
+// function FN's slice of the row) into the same block sums, rows written once.
+template <int MASK, int CB>
+__global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__restrict__ buf, int P, int N, int C,
+                                                                const float *__restrict__ means,
+                                                                const float *__restrict__ values,
+                                                                const float *__restrict__ conics,
+                                                                const float *__restrict__ samples,
+                                                                const float *__restrict__ hs,
+                                                                float *__restrict__ dmeans,
+                                                                float *__restrict__ dvalues,
+                                                                float *__restrict__ dconics) {
+    constexpr int NV = 9 + CB, SKU = mask_ku(MASK);
+    __shared__ float part[kWavesPerBlock][NV];
+    const Hdr h = hdr_of(buf);
+    if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_mc writes the NaN)
+    const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
+    const int nch = min(CB, C);
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    for (int b = blockIdx.x; b < h.nbig; b += gridDim.x) {
+        const int g = gids[h.nsmall + b];
+        float m[3], c[6];
+        for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+        for (int q = 0; q < 6; ++q) c[q] = conics[(int64_t)g * 6 + q];
+        float v[NV];
+        for (int k = 0; k < NV; ++k) v[k] = 0.0f;
+        for (int sid = threadIdx.x; sid < N; sid += kBlock) {
+            const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
+            const float *hrow = hs + (int64_t)sid * SKU * C;
+            for_mask<MASK>([&](auto fc) {
+                constexpr int FN = decltype(fc)::value;
+                bwd_pair<FN, CB>(m, c, values, g, C, 0, nch, sp, hrow + mask_off(MASK, FN) * C, v, v + 3, v + 9);
+            });
+        }
+        for (int k = 0; k < NV; ++k)
+            for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+        if (lane == 0)
+            for (int k = 0; k < NV; ++k) part[w][k] = v[k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t[NV];
+            for (int k = 0; k < NV; ++k) {
+                t[k] = 0.0f;
+                for (int q = 0; q < kWavesPerBlock; ++q) t[k] += part[q][k];
+            }
+            bwd_store<CB>(g, C, 0, nch, t, t + 3, t + 9, dmeans, dvalues, dconics);
+        }
+        __syncthreads();
+    }
+}
+
+// The sample gradient of several functions at C = 2..4: k_vol_sgrad's lane (the tensor H per channel
+// in registers, hv per pair) with phi and g summed over the mask's functions, as k_vol_sgrad_m does.
+// Three sums per lane, one store, no cross-lane sums.
+template <int MASK, int CB>
+__global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__ buf, int P, int N, int C,
+                                                        const float *__restrict__ means,
+                                                        const float *__restrict__ values,
+                                                        const float *__restrict__ conics,
+                                                        const float *__restrict__ samples, VDLs dLs,
+                                                        float *__restrict__ dsamples) {
+    constexpr int SKU = mask_ku(MASK);
+    __shared__ VCand<CB> cand[kWave];
+    const Hdr &h = hdr_of(buf);
+    const int lane = threadIdx.x;
+    const int nch = min(CB, C);
+    if (vol_stale(buf, h, P, N)) {  // stale buffer / inputs: loud
+        for (int64_t i = (int64_t)blockIdx.x * kWave + lane; i < (int64_t)N * 3; i += (int64_t)gridDim.x * kWave)
+            dsamples[i] = NAN;
+        return;
+    }
+    const Bin bin = bin_of(buf, h);
+    for (int cell = blockIdx.x; cell < h.ncells; cell += gridDim.x) {
+        const int sb = bin.sstart[cell], se = bin.sstart[cell + 1];
+        const int cc[3] = {cell % h.n[0], (cell / h.n[0]) % h.n[1], cell / (h.n[0] * h.n[1])};
+        for (int j0 = sb; j0 < se; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool active = j < se;
+            const int sid = active ? bin.sids[j] : 0;
+            float s[3];
+            for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
+            float hh[SKU][CB];  // the tensors H per channel, function after function
+            for (int u = 0; u < SKU; ++u)
+                for (int ch = 0; ch < CB; ++ch) hh[u][ch] = 0.0f;
+            if (active)
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value, KU = VTr<FN>::KU, K = VTr<FN>::K, O = mask_off(MASK, FN);
+                    const float *__restrict__ dL = dLs.p[FN];
+#pragma unroll
+                    for (int f = 0; f < K; ++f)
+#pragma unroll
+                        for (int ch = 0; ch < CB; ++ch)
+                            if (ch < nch) hh[O + umap<FN>(f)][ch] += dL[((int64_t)sid * K + f) * C + ch];
+#pragma unroll
+                    for (int u = 0; u < KU; ++u)
+                        for (int ch = 0; ch < CB; ++ch) hh[O + u][ch] *= vol_inv_mult<FN>(u);
+                });
+            float ds[3] = {0.0f, 0.0f, 0.0f};
+            auto values_of = [&](float *vr, int g) {
+                for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + ch] : 0.0f;
+            };
+            auto eval = [&](const float *m, const float *c, const float *vr) {
+                float X[3], a[3], G;
+                if (!pair_eval(m, s, c, X, G, a)) return;
+                float hv[SKU];
+#pragma unroll
+                for (int u = 0; u < SKU; ++u) {
+                    hv[u] = 0.0f;
+                    for (int ch = 0; ch < CB; ++ch) hv[u] += vr[ch] * hh[u][ch];
+                }
+                const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
+                float phi = 0.0f, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
+                for_mask<MASK>([&](auto fc) {
+                    constexpr int FN = decltype(fc)::value;
+                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, g, e);
+                });
+                sg_add(G, phi, a, c, g, ds);
+            };
+            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            if (active) {
+                for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
+                    const int g = bin.gids[q];
+                    float m[3], c[6], vr[CB];
+                    for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
+                    for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
+                    values_of(vr, g);
+                    eval(m, c, vr);
+                }
+                for (int d = 0; d < 3; ++d) dsamples[(int64_t)sid * 3 + d] = ds[d];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ launches
 struct VArgs {  // what every launch takes
     const char *buf;
@@ -1579,6 +1988,36 @@ static void launch_sgrad(const VArgs &a, const float *dL, float *ds) {
     for (int cb = 0; cb < a.C; cb += CB)
         k_vol_sgrad<FN, CB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
                                                               a.samples, dL, ds);
+}
+
+// C = 2..4: two or more functions, the one channel block of 4
+constexpr int kVolFusedCB = DGS_VOLUME_FUSED_MAX_C;
+template <int MASK>
+static void launch_fwd_mc(const VArgs &a, float *const *outs) {
+    VOuts o;
+    for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? outs[f] : nullptr;
+    k_vol_forward_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
+                                                                          a.conics, a.samples, o);
+}
+template <int MASK>
+static void launch_bwd_mc(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc) {
+    const int64_t nh = (int64_t)a.N * a.C;
+    for_mask<MASK>([&](auto fc) {
+        constexpr int FN = decltype(fc)::value;
+        k_vol_hsum_cat_c<FN><<<(unsigned)((nh + kBlock - 1) / kBlock), kBlock, 0, a.s>>>(
+            a.N, a.C, dLs[FN], hs, mask_ku(MASK) * a.C, mask_off(MASK, FN) * a.C);
+    });
+    k_vol_backward_mc<MASK, kVolFusedCB><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
+                                                                           a.conics, a.samples, hs, dm, dv, dc);
+    k_vol_backward_big_mc<MASK, kVolFusedCB><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
+                                                                      a.conics, a.samples, hs, dm, dv, dc);
+}
+template <int MASK>
+static void launch_sgrad_mc(const VArgs &a, const float *const *dLs, float *ds) {
+    VDLs d;
+    for (int f = 0; f < 4; ++f) d.p[f] = (MASK >> f) & 1 ? dLs[f] : nullptr;
+    k_vol_sgrad_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
+                                                                        a.conics, a.samples, d, ds);
 }
 
 // the masks of the forward kernels (all 15) and of the fused backward (two or more functions)
@@ -1889,6 +2328,121 @@ extern "C" int dgs_volume_backward_samples(int mask, int P, int N, int C, const 
             X(0, 4) X(0, 8) X(1, 4) X(1, 8) X(2, 4) X(2, 8) X(3, 4)
 #undef X
         }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+// ---- the *_fused entries: several functions at 2 <= C <= DGS_VOLUME_FUSED_MAX_C take the _mc
+// kernels; a single-bit mask or C = 1 is the *_multi entry itself (the same check, the same
+// launches); several functions above the limit are refused (the caller's fallback).
+static bool fused_mc(int mask, int C) {
+    return mask >= 1 && mask <= 15 && (mask & (mask - 1)) != 0 && C >= 2 && C <= DGS_VOLUME_FUSED_MAX_C;
+}
+// the checks of the _mc path; `forwards`: the call belongs to the *_multi entry
+static int vol_check_fused(int mask, int P, int N, int C, const void *binning, size_t bytes, bool &forwards) {
+    forwards = !fused_mc(mask, C);
+    if (forwards) {
+        if (mask >= 1 && mask <= 15 && (mask & (mask - 1)) != 0 && C > DGS_VOLUME_FUSED_MAX_C && P >= 0 && N >= 0)
+            return fail(DGS_ERR_ARG, "dgs_volume_*_fused: several functions need C <= 4 (DGS_VOLUME_FUSED_MAX_C); "
+                                     "call the per-function entry points and add");
+        return DGS_OK;
+    }
+    if (P < 0 || N < 0) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
+    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+    return DGS_OK;
+}
+
+extern "C" size_t dgs_volume_workspace_size_fused(int mask, int P, int N, int C, int backward) {
+    if (!fused_mc(mask, C)) return vol_workspace(mask, N, C, backward);
+    if (!backward || N <= 0) return 0;
+    return (size_t)N * mask_ku(mask) * C * 4;  // hs[N][unique components of the mask][C]
+}
+
+extern "C" int dgs_volume_forward_fused(int mask, int P, int N, int C, const float *means, const float *values,
+                                        const float *conics, const float *samples, const void *binning,
+                                        size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug) {
+    bool forwards;
+    if (int rc = vol_check_fused(mask, P, N, C, binning, binning_bytes, forwards)) return rc;
+    if (forwards)
+        return vol_forward(true, mask, P, N, C, means, values, conics, samples, binning, binning_bytes, outs, stream, debug);
+    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_fused: outs required");
+    if (N == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    switch (mask) {
+#define X(M) case M: launch_fwd_mc<M>(a, outs); break;
+        DGS_VOL_MASKS_FUSED(X)
+#undef X
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_fused(int mask, int P, int N, int C, const float *means, const float *values,
+                                         const float *conics, const float *samples, const float *const *dL_douts,
+                                         const void *binning, size_t binning_bytes, float *dL_dmeans,
+                                         float *dL_dvalues, float *dL_dconics, void *workspace,
+                                         size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    bool forwards;
+    if (int rc = vol_check_fused(mask, P, N, C, binning, binning_bytes, forwards)) return rc;
+    if (forwards)
+        return vol_backward(true, mask, P, N, C, means, values, conics, samples, dL_douts, binning, binning_bytes,
+                            dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_fused: dL_douts required");
+    if (workspace_bytes < dgs_volume_workspace_size_fused(mask, P, N, C, 1) || (N > 0 && P > 0 && !workspace))
+        return fail(DGS_ERR_ARG, "dgs_volume_backward_fused: workspace missing or too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) return DGS_OK;
+    if (N == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * C * 4, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
+        return DGS_OK;
+    }
+    for (int f = 0; f < 4; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_fused: a dL_dout of the mask is NULL");
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    float *hs = static_cast<float *>(workspace);
+    switch (mask) {
+#define X(M) case M: launch_bwd_mc<M>(a, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics); break;
+        DGS_VOL_MASKS_FUSED(X)
+#undef X
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_samples_fused(int mask, int P, int N, int C, const float *means,
+                                                 const float *values, const float *conics, const float *samples,
+                                                 const float *const *dL_douts, const void *binning,
+                                                 size_t binning_bytes, float *dL_dsamples, void *workspace,
+                                                 size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    bool forwards;
+    if (int rc = vol_check_fused(mask, P, N, C, binning, binning_bytes, forwards)) return rc;
+    if (forwards)
+        return dgs_volume_backward_samples(mask, P, N, C, means, values, conics, samples, dL_douts, binning,
+                                           binning_bytes, dL_dsamples, workspace, workspace_bytes, stream, debug);
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_fused: dL_douts required");
+    if (N == 0) return DGS_OK;
+    if (!dL_dsamples) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_fused: dL_dsamples required");
+    for (int f = 0; f < 4; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_fused: a dL_dout of the mask is NULL");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dsamples, 0, (size_t)N * 12, s));
+        return DGS_OK;
+    }
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    switch (mask) {
+#define X(M) case M: launch_sgrad_mc<M>(a, dL_douts, dL_dsamples); break;
+        DGS_VOL_MASKS_FUSED(X)
+#undef X
     }
     DGS_LAUNCH_CHECK(s, debug);
     return DGS_OK;

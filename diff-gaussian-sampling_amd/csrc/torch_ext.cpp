@@ -1076,10 +1076,11 @@ std::tuple<Tensor, Tensor, Tensor> VolumeBackward(int function, const Tensor &me
     return std::make_tuple(dm, dv, dc);
 }
 
-// Fused functions at D = 3 (dgs_volume_{forward,backward}_multi): `codes` holds distinct codes
-// 0..3; the outputs come back in that order.  Several functions at C = 1 share one walk of the
-// candidates; otherwise (one function, or C > 1, which the C entry refuses) the per-function
-// kernels run in turn and the backward adds their gradients.
+// Fused functions at D = 3 (dgs_volume_{forward,backward}_fused): `codes` holds distinct codes
+// 0..3; the outputs come back in that order.  Several functions at C <= DGS_VOLUME_FUSED_MAX_C
+// share one walk of the candidates; otherwise (one function, or more channels, which the C entry
+// refuses) the per-function kernels run in turn and the backward adds their gradients.
+static bool vol_one_walk(size_t ncodes, int64_t C) { return ncodes > 1 && C >= 1 && C <= DGS_VOLUME_FUSED_MAX_C; }
 std::vector<Tensor> VolumeForwardMulti(const std::vector<int64_t> &codes, const Tensor &means_in,
                                        const Tensor &values_in, const Tensor &conics_in, const Tensor &samples_in,
                                        const Tensor &binning_in, const bool debug) {
@@ -1091,7 +1092,7 @@ std::vector<Tensor> VolumeForwardMulti(const std::vector<int64_t> &codes, const 
     TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
     const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
     std::vector<Tensor> outs;
-    if (codes.size() == 1 || C != 1) {
+    if (!vol_one_walk(codes.size(), C)) {
         for (int64_t f : codes)
             outs.push_back(VolumeForward((int)f, means_in, values_in, conics_in, samples_in, binning_in, debug));
         return outs;
@@ -1105,9 +1106,10 @@ std::vector<Tensor> VolumeForwardMulti(const std::vector<int64_t> &codes, const 
         ptr[f] = outs.back().data_ptr<float>();
     }
     if (N == 0) return outs;
-    check(dgs_volume_forward_multi(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
-                                   conics.data_ptr<float>(), samples.data_ptr<float>(), binning.data_ptr(),
-                                   (size_t)binning.numel(), ptr, as_dgs(cur_stream()), debug ? 1 : 0),
+    const auto fwd = C == 1 ? dgs_volume_forward_multi : dgs_volume_forward_fused;  // (C = 1: the branch it had)
+    check(fwd(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+              conics.data_ptr<float>(), samples.data_ptr<float>(), binning.data_ptr(), (size_t)binning.numel(), ptr,
+              as_dgs(cur_stream()), debug ? 1 : 0),
           "volume_forward_multi");
     return outs;
 }
@@ -1123,7 +1125,7 @@ std::tuple<Tensor, Tensor, Tensor> VolumeBackwardMulti(const std::vector<int64_t
     const Tensor binning = u8(binning_in, "binning_buffer");
     vol_shapes(means, conics, samples);
     const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
-    if (codes.size() == 1 || C != 1) {
+    if (!vol_one_walk(codes.size(), C)) {
         auto g = VolumeBackward((int)codes[0], means_in, values_in, conics_in, samples_in, binning_in, dLs_in[0], debug);
         for (size_t i = 1; i < codes.size(); ++i) {
             auto h = VolumeBackward((int)codes[i], means_in, values_in, conics_in, samples_in, binning_in, dLs_in[i],
@@ -1146,19 +1148,22 @@ std::tuple<Tensor, Tensor, Tensor> VolumeBackwardMulti(const std::vector<int64_t
     Tensor dm = torch::zeros({P, 3}, means.options()), dv = torch::zeros({P, C}, means.options());
     Tensor dc = torch::zeros({P, 6}, means.options());
     if (P == 0) return std::make_tuple(dm, dv, dc);
-    const size_t ws = dgs_volume_workspace_size_multi(mask, (int)P, (int)N, (int)C, 1);
+    const auto wsz = C == 1 ? dgs_volume_workspace_size_multi : dgs_volume_workspace_size_fused;
+    const auto bwd = C == 1 ? dgs_volume_backward_multi : dgs_volume_backward_fused;  // (C = 1: the branch it had)
+    const size_t ws = wsz(mask, (int)P, (int)N, (int)C, 1);
     Tensor work = torch::empty({(int64_t)std::max<size_t>(ws, 4)}, means.options().dtype(torch::kUInt8));
-    check(dgs_volume_backward_multi(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
-                                    conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(),
-                                    (size_t)binning.numel(), dm.data_ptr<float>(), dv.data_ptr<float>(),
-                                    dc.data_ptr<float>(), work.data_ptr(), ws, as_dgs(cur_stream()), debug ? 1 : 0),
+    check(bwd(mask, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+              conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(), (size_t)binning.numel(),
+              dm.data_ptr<float>(), dv.data_ptr<float>(), dc.data_ptr<float>(), work.data_ptr(), ws,
+              as_dgs(cur_stream()), debug ? 1 : 0),
           "volume_backward_multi");
     return std::make_tuple(dm, dv, dc);
 }
 
-// dL / d samples at D = 3 (dgs_volume_backward_samples): [N, 3].  Several codes at C = 1 share one
-// walk; at C > 1 (which the C entry refuses for several) the single-function calls run in turn and
-// their results are added, as VolumeBackwardMulti's fallback does.
+// dL / d samples at D = 3 (dgs_volume_backward_samples{,_fused}): [N, 3].  Several codes at
+// C <= DGS_VOLUME_FUSED_MAX_C share one walk; with more channels (which the C entry refuses for
+// several) the single-function calls run in turn and their results are added, as
+// VolumeBackwardMulti's fallback does.
 Tensor VolumeSamplesBackward(const std::vector<int64_t> &codes, const Tensor &means_in, const Tensor &values_in,
                              const Tensor &conics_in, const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
                              const Tensor &binning_in, const bool debug) {
@@ -1179,16 +1184,17 @@ Tensor VolumeSamplesBackward(const std::vector<int64_t> &codes, const Tensor &me
     }
     Tensor ds = torch::zeros({N, 3}, means.options());
     if (N == 0 || P == 0 || C == 0) return ds;
+    const bool mc = C > 1 && vol_one_walk(codes.size(), C);  // (else: the branch it had)
     auto call = [&](int m, const float *const *ptr, Tensor &out) {
         const size_t ws = dgs_volume_sample_grad_workspace_size(m, (int)P, (int)N, (int)C);
         Tensor work = torch::empty({(int64_t)std::max<size_t>(ws, 4)}, means.options().dtype(torch::kUInt8));
-        check(dgs_volume_backward_samples(m, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
-                                          conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(),
-                                          (size_t)binning.numel(), out.data_ptr<float>(), work.data_ptr(), ws,
-                                          as_dgs(cur_stream()), debug ? 1 : 0),
+        const auto sg = mc ? dgs_volume_backward_samples_fused : dgs_volume_backward_samples;
+        check(sg(m, (int)P, (int)N, (int)C, means.data_ptr<float>(), values.data_ptr<float>(),
+                 conics.data_ptr<float>(), samples.data_ptr<float>(), ptr, binning.data_ptr(), (size_t)binning.numel(),
+                 out.data_ptr<float>(), work.data_ptr(), ws, as_dgs(cur_stream()), debug ? 1 : 0),
               "volume_samples_backward");
     };
-    if (codes.size() == 1 || C == 1) {
+    if (codes.size() == 1 || C == 1 || mc) {
         const float *ptr[4] = {nullptr, nullptr, nullptr, nullptr};
         for (size_t i = 0; i < codes.size(); ++i) ptr[codes[i]] = dLs[i].data_ptr<float>();
         call(mask, ptr, ds);

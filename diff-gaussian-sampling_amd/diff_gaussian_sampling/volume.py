@@ -146,11 +146,13 @@ class _SampleVolumeMultiSG(torch.autograd.Function):
 
 def sample_volume_multi(functions, means, values, conics, samples, binning, debug=False, sample_grad=False):
     """Several of the four functions (distinct names or codes) of a D = 3 field at `samples`;
-    returns their outputs in the order asked.  At C = 1 they share one walk of the candidates,
-    forward and backward (include/dgs_volume.h, dgs_volume_*_multi); each output is bitwise the
-    one `sample_volume` returns.  An output whose gradient is None is left out of the backward.
+    returns their outputs in the order asked.  Up to C = 4 (a velocity field, velocity and pressure)
+    they share one walk of the candidates, forward and backward (include/dgs_volume.h,
+    dgs_volume_*_multi at C = 1, dgs_volume_*_fused at C = 2..4); with more channels the
+    per-function kernels run in turn and their gradients are added.  Each output is bitwise the one
+    `sample_volume` returns.  An output whose gradient is None is left out of the backward.
     sample_grad=True: as for `sample_volume`, the gradient of `samples` over the live outputs (one
-    walk at C = 1, the per-function calls added at C > 1)."""
+    walk up to C = 4, the per-function calls added above)."""
     codes = tuple(FUNCTION_CODES[f] if isinstance(f, str) else int(f) for f in functions)
     fn = _SampleVolumeMultiSG if sample_grad else _SampleVolumeMulti
     return fn.apply(codes, means, values, conics, samples, binning, debug)
@@ -203,7 +205,8 @@ class VolumeSampler:
 
     def sample_gaussians_multi(self, *functions):
         """Several functions ("gaussian", "derivative", "laplacian", "third" or 0..3) in one
-        call; returns a tuple in the order asked (sample_volume_multi)."""
+        call; returns a tuple in the order asked (sample_volume_multi: one walk of the candidates
+        for fields of up to four channels)."""
         self._rebin_if_changed()
         return sample_volume_multi(functions, self.means, self.values, self.conics, self.samples,
                                    self.binning, self.debug, self.sample_grad)

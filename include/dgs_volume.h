@@ -104,6 +104,39 @@ int dgs_volume_backward_samples(int mask, int P, int N, int C, const float *mean
                                 const void *binning, size_t binning_bytes, float *dL_dsamples,
                                 void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
 
+/* Fused functions of a multi-channel field: the *_multi / *_samples calls above with one walk of
+ * the candidates also for two or more functions at 2 <= C <= DGS_VOLUME_FUSED_MAX_C (a velocity
+ * field, C = 3, or velocity and pressure, C = 4).  Same argument lists.
+ *   - a single-bit mask (any C) or C = 1 (any mask): the call is dgs_volume_forward_multi /
+ *     dgs_volume_backward_multi / dgs_volume_backward_samples itself, the same checks, the same
+ *     launches, bit-identical results;
+ *   - two or more functions at 2 <= C <= DGS_VOLUME_FUSED_MAX_C: one walk for every function and
+ *     every channel.  outs[f] / dL_douts[f] are [N][3^f][C].  Each output is bit-identical to
+ *     dgs_volume_forward's and does not depend on the other functions of the mask; the gradients
+ *     equal the sum of the per-function calls' to rounding (another order of the same sums), with
+ *     no atomics, so repeated calls are bit-identical.  Backward workspace: N * (unique components
+ *     of the mask's functions) * C * 4 bytes; the forward and the sample gradient need none;
+ *   - two or more functions above the limit: DGS_ERR_ARG (call the per-function entry points and
+ *     add), and the workspace size is 0.
+ * Edge sizes, the stale buffer / changed input guard (NaN in every output of the mask, every
+ * gradient and dL_dsamples), DGS_ERR_BUFFER for a missing or short binning and the ordering of
+ * calls on one binning are those of the calls above; no host sync, no allocation.  New exported
+ * functions only: DGS_ABI_VERSION is unchanged. */
+#define DGS_VOLUME_FUSED_MAX_C 4
+size_t dgs_volume_workspace_size_fused(int mask, int P, int N, int C, int backward);
+int dgs_volume_forward_fused(int mask, int P, int N, int C, const float *means, const float *values,
+                             const float *conics, const float *samples, const void *binning,
+                             size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug);
+int dgs_volume_backward_fused(int mask, int P, int N, int C, const float *means, const float *values,
+                              const float *conics, const float *samples, const float *const *dL_douts,
+                              const void *binning, size_t binning_bytes, float *dL_dmeans,
+                              float *dL_dvalues, float *dL_dconics, void *workspace,
+                              size_t workspace_bytes, dgs_stream_t stream, int debug);
+int dgs_volume_backward_samples_fused(int mask, int P, int N, int C, const float *means, const float *values,
+                                      const float *conics, const float *samples, const float *const *dL_douts,
+                                      const void *binning, size_t binning_bytes, float *dL_dsamples,
+                                      void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
+
 /* Diagnostic (not on any reference API): counts[0] = pairs the forward evaluates (candidates
  * inside their own cut box), counts[1] = live pairs (G = expf(power) > 0).  Host, syncs;
  * DGS_ERR_BUFFER when the inputs differ from the binned ones. */

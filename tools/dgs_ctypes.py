@@ -320,3 +320,67 @@ def aggregate_neighbors_backward(features, transform, queries, keys, frequencies
                                  _ptr(_order(idx, P)), _ptr(g), *[_ptr(o) for o in outs], _ptr(ws), ws.numel(),
                                  _stream(), int(bool(debug))))
     return tuple(outs)
+
+
+# ---- D = 3 fields: fused functions (include/dgs_volume.h, dgs_volume_*_fused and the *_multi /
+# *_samples entries they extend; not on the reference API).  `binning` is the uint8 tensor of
+# dgs_volume_preprocess (the extension's _C.volume_preprocess returns it).
+_lib.dgs_volume_workspace_size_fused.restype = _SZ
+_lib.dgs_volume_workspace_size_fused.argtypes = [_I] * 5
+_lib.dgs_volume_workspace_size_multi.restype = _SZ
+_lib.dgs_volume_workspace_size_multi.argtypes = [_I] * 5
+for _n in ("fused", "multi"):
+    getattr(_lib, "dgs_volume_forward_" + _n).argtypes = [_I] * 4 + [_P] * 4 + [_P, _SZ, _PP, _P, _I]
+    getattr(_lib, "dgs_volume_backward_" + _n).argtypes = [_I] * 4 + [_P] * 4 + [_PP, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _I]
+for _n in ("dgs_volume_backward_samples_fused", "dgs_volume_backward_samples"):
+    getattr(_lib, _n).argtypes = [_I] * 4 + [_P] * 4 + [_PP, _P, _SZ, _P, _P, _SZ, _P, _I]
+
+
+def volume_workspace_size_fused(mask, P, N, C, backward):
+    return _lib.dgs_volume_workspace_size_fused(mask, P, N, C, backward)
+
+
+def volume_forward_fused(codes, means, values, conics, samples, binning, debug, entry="fused"):
+    """Outputs [N, 3^f, C] of the functions `codes` (0..3, each once) in the order given.
+    entry="multi" calls dgs_volume_forward_multi instead (several functions: C = 1 only)."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    mask = sum(1 << c for c in codes)
+    outs = {c: torch.zeros((N,) + (3,) * c + (C,), device=means.device) for c in codes}
+    ptrs = _PP(*[outs[c].data_ptr() if c in outs else None for c in range(4)])
+    _check(getattr(_lib, "dgs_volume_forward_" + entry)(
+        mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), _ptr(binning), binning.numel(), ptrs,
+        _stream(), int(bool(debug))))
+    return [outs[c] for c in codes]
+
+
+def volume_backward_fused(codes, means, values, conics, samples, dLs, binning, debug, entry="fused", workspace=None):
+    """Gradients (dmeans, dvalues, dconics) of sum_f <dLs[f], out_f>.  workspace: a uint8 tensor to
+    use instead of one of the required size (it may be larger)."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    dLs = {c: _f32(d) for c, d in zip(codes, dLs)}
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    mask = sum(1 << c for c in codes)
+    dm, dv, dc = (torch.zeros(P, k, device=means.device) for k in (3, C, 6))
+    ptrs = _PP(*[dLs[c].data_ptr() if c in dLs else None for c in range(4)])
+    if workspace is None:
+        size = getattr(_lib, "dgs_volume_workspace_size_" + entry)(mask, P, N, C, 1)
+        workspace = torch.empty(size, dtype=torch.uint8, device=means.device)
+    _check(getattr(_lib, "dgs_volume_backward_" + entry)(
+        mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning), binning.numel(),
+        _ptr(dm), _ptr(dv), _ptr(dc), _ptr(workspace), workspace.numel(), _stream(), int(bool(debug))))
+    return dm, dv, dc
+
+
+def volume_samples_backward_fused(codes, means, values, conics, samples, dLs, binning, debug, entry="fused"):
+    """dL/dsamples [N, 3] of sum_f <dLs[f], out_f>; entry="multi" calls dgs_volume_backward_samples."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    dLs = {c: _f32(d) for c, d in zip(codes, dLs)}
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    mask = sum(1 << c for c in codes)
+    ds = torch.zeros(N, 3, device=means.device)
+    ptrs = _PP(*[dLs[c].data_ptr() if c in dLs else None for c in range(4)])
+    fn = _lib.dgs_volume_backward_samples_fused if entry == "fused" else _lib.dgs_volume_backward_samples
+    _check(fn(mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
+              binning.numel(), _ptr(ds), None, 0, _stream(), int(bool(debug))))
+    return ds

@@ -1,17 +1,18 @@
 """Times the fused D = 3 multi-function call against the per-function calls on one binning.
 
     python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
-                                       [--rounds 3] [--steps 3] [--separate-only [--C 3]]
+                                       [--rounds 3] [--steps 3] [--C 3] [--separate-only]
 
-The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice, C = 1).  After settle
+The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice; C = 1 unless --C).  After settle
 steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
 hits both alike; each figure is the median over the rounds of the mean ms per forward +
 backward step (preprocess excluded).  Prints one JSON line: fused_ms, separate_ms (the sum of the
 per-function calls, same outputs and gradients), per-function step times `single_ms`, the speedup,
 and `fused_over_last`, the fused step against the most expensive (last named) function alone.
 --separate-only times the per-function calls only (a package without the fused call, for A/B
-runs through tools/ab.py --script); --C sets the channel count of those calls (the fused call
-covers C = 1 only, so --C needs --separate-only).
+runs through tools/ab.py --script); --C sets the channel count (the fused call shares one walk up
+to C = 4; with more channels, or in a package from before that, it is the per-function calls added:
+the yardstick of an A/B run through tools/ab.py --script against a build of the parent commit).
 """
 import argparse
 import json
@@ -38,10 +39,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--settle", type=int, default=2)
     ap.add_argument("--separate-only", action="store_true")
-    ap.add_argument("--C", type=int, default=1, help="channels (other than 1: only with --separate-only)")
+    ap.add_argument("--C", type=int, default=1, help="channels")
     args = ap.parse_args()
-    if args.C != 1 and not args.separate_only:
-        ap.error("--C other than 1 needs --separate-only (the fused call covers C = 1)")
     C = args.C
     fns = args.functions.split(",")
     dev = torch.device("cuda:0")

@@ -4,9 +4,13 @@ yardstick, in alternating child processes on one GPU (the pattern of tools/bench
 clock drift and the box hit every kind alike).
 
     python tools/volume_sample_grad_bench.py [--rounds 3] [--steps 10] [--out profiles/volume_sample_grad_bench.json]
+                                             [--C 3] [--kinds sg:gaussian+derivative+laplacian] [--pkgs base,variants/NAME]
 
-Kinds: sg:<function> and sg:all (mask 15) -- the new call, whole (the input check and the one
-kernel); fwd:<function> -- the forward call on the same binning.  The yardstick of sg:<f> is the
+Kinds: sg:<function>, sg:all (mask 15) and sg:<f>+<g>+... (that mask) -- the new call, whole (the
+input check and the kernels); fwd:<function> -- the forward call on the same binning.  --C sets the
+channel count (several functions share one walk up to C = 4; above, the per-function calls are added).
+--pkgs times every kind under several packages in turn (base: the in-tree one; variants/NAME: a
+tools/variant.sh build, e.g. of the parent commit), reported as kind@package.  The yardstick of sg:<f> is the
 forward of the next-higher function (the same walk, the same G and a, terms one order lower; DESIGN.md
 4.9), with the section's margin of 1.25x; the forward code is the parent commit's, which this
 feature leaves unchanged.  sg:third and sg:all have no yardstick: they are reported alone, sg:all
@@ -30,13 +34,13 @@ MARGIN = 1.25
 
 
 def child(a):
-    sys.path.insert(0, os.path.join(REPO, "diff-gaussian-sampling_amd"))
+    sys.path.insert(0, os.environ.get("DGS_PKG_ROOT", os.path.join(REPO, "diff-gaussian-sampling_amd")))
     import torch
     import diff_gaussian_sampling as dgs
     from diff_gaussian_sampling import synthetic as syn
     assert torch.cuda.is_available(), "needs the GPU"
     dev = torch.device("cuda:0")
-    means, values, _, conics = (t.to(dev) for t in syn.gaussians3(a.P, 1, seed=0))
+    means, values, _, conics = (t.to(dev) for t in syn.gaussians3(a.P, a.C, seed=0))
     samples = syn.grid_samples3(a.grid3).to(dev)
     N = samples.shape[0]
     buf = dgs._C.volume_preprocess(means, conics, samples, False)
@@ -45,9 +49,9 @@ def child(a):
         code = FUNCS.index(f)
         call = lambda: dgs._C.volume_forward(code, means, values, conics, samples, buf, False)  # noqa: E731
     else:
-        codes = [0, 1, 2, 3] if f == "all" else [FUNCS.index(f)]
+        codes = [0, 1, 2, 3] if f == "all" else [FUNCS.index(x) for x in f.split("+")]
         gen = torch.Generator().manual_seed(5)
-        dLs = [torch.randn((N, 3 ** k, 1), generator=gen).to(dev) for k in codes]
+        dLs = [torch.randn((N, 3 ** k, a.C), generator=gen).to(dev) for k in codes]
         call = lambda: dgs._C.volume_samples_backward(codes, means, values, conics, samples, dLs, buf, False)  # noqa: E731
     for _ in range(a.warmup):
         call()
@@ -74,26 +78,34 @@ def main():
     ap.add_argument("--P", type=int, default=1_000_000)
     ap.add_argument("--grid3", type=int, default=64)
     ap.add_argument("--kinds", default=",".join(KINDS))
+    ap.add_argument("--C", type=int, default=1)
+    ap.add_argument("--pkgs", default="base", help="packages timed in turn: base or variants/NAME")
     ap.add_argument("--out", default="")
     ap.add_argument("--child", default="")
     ap.add_argument("--count", action="store_true")
     a = ap.parse_args()
     if a.child:
         return child(a)
-    kinds = a.kinds.split(",")
+    pkgs = a.pkgs.split(",")
+    kinds = [k if p == "base" else k + "@" + p for k in a.kinds.split(",") for p in pkgs]
     runs = {k: [] for k in kinds}
     extra = {}
     for r in range(a.rounds):
         for i, k in enumerate(kinds):
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", k, "--steps", str(a.steps), "--warmup",
-                   str(a.warmup), "--P", str(a.P), "--grid3", str(a.grid3)]
+            kind, _, pkg = k.partition("@")
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", kind, "--steps", str(a.steps), "--warmup",
+                   str(a.warmup), "--P", str(a.P), "--grid3", str(a.grid3), "--C", str(a.C)]
             if r == 0 and i == 0:
                 cmd.append("--count")
-            out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+            env = dict(os.environ)
+            if pkg:
+                env["DGS_PKG_ROOT"] = os.path.join(REPO, pkg)
+            out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
             if out.returncode != 0:
                 sys.stderr.write(out.stderr[-3000:])
                 sys.exit(out.returncode)
             j = json.loads(out.stdout.strip().splitlines()[-1])
+            j["kind"] = k
             runs[k].append(j)
             for w in ("W_eval", "W_live"):
                 if w in j:
@@ -101,7 +113,7 @@ def main():
             print(r, json.dumps(j), flush=True)
     med = {k: statistics.median(j["ms"] for j in js) for k, js in runs.items()}
     ratio = {k: med[k] / med[y] for k, y in YARDSTICK.items() if k in med and y in med}
-    res = {"P": a.P, "N": a.grid3 ** 3, "grid3": a.grid3, "D": 3, "C": 1, "rounds": a.rounds, "steps": a.steps,
+    res = {"P": a.P, "N": a.grid3 ** 3, "grid3": a.grid3, "D": 3, "C": a.C, "rounds": a.rounds, "steps": a.steps,
            "median_ms": med, "yardstick": {k: y for k, y in YARDSTICK.items() if k in ratio},
            "ratio_to_yardstick": ratio, "margin": MARGIN, "within_margin": {k: r <= MARGIN for k, r in ratio.items()}}
     singles = ["sg:" + f for f in FUNCS]
