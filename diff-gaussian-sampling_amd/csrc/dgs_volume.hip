@@ -29,6 +29,9 @@
 //   * several functions of a field of 2..4 channels: the _mc kernels ("mask, channels", below the
 //     sample gradients), one walk for every function and channel in the forward, the backward
 //     (moment form, its own loop nest walk_samples) and the sample gradient.
+//   * a fifth function, the trace of the laplacian (code 4, bit 4 of a mask, one component per
+//     channel; the dgs_volume_*_ops entries): new instantiations of the same templates, alone at any
+//     C and fused with functions 0, 1, 3 up to C = 4 ("Trace Laplacian").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -90,22 +93,29 @@ __host__ __device__ constexpr int sort3_idx(int i, int j, int k) {
 
 // Function masks (bit f = function f).  The unique (symmetric) components of a mask's functions:
 // 1, 3, 6 and 10 of the 1, 3, 9 and 27 full ones; every other count derives from this one.
+// Function 4 (bit 4) is the trace of the laplacian, one component ("Trace
+// Laplacian"); it comes last in a concatenated row and never shares a mask with the laplacian.
 __host__ __device__ constexpr int mask_ku(int mask) {
-    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0);
+    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0) + (mask & 16 ? 1 : 0);
 }
 // offset of function f's unique components in a concatenated row of the mask's functions
 __host__ __device__ constexpr int mask_off(int mask, int f) { return mask_ku(mask & ((1 << f) - 1)); }
-__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & 4 ? 2 : mask & 2 ? 1 : 0; }
+// the order of the mask's highest function (the trace is of order 2: vol_mom_add<TOP>)
+__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & (4 | 16) ? 2 : mask & 2 ? 1 : 0; }
+constexpr int kFnTrace = DGS_VOLUME_FN_LAPLACIAN_TRACE;
+// The kernels' pointer structs (VOuts, VDLs) have one slot per function code 0..3; the trace takes
+// the laplacian's, which a mask with the trace never uses.
+__host__ __device__ constexpr int fn_slot(int fn) { return fn == kFnTrace ? 2 : fn; }
 
 template <int FN>
 struct VTr {
-    static constexpr int KU = mask_ku(1 << FN), K = FN == 0 ? 1 : FN == 1 ? 3 : FN == 2 ? 9 : 27;
+    static constexpr int KU = mask_ku(1 << FN), K = FN == 0 || FN == kFnTrace ? 1 : FN == 1 ? 3 : FN == 2 ? 9 : 27;
 };
 
 // unique component of the full output index f (row-major over the 3^FN indices)
 template <int FN>
 __host__ __device__ constexpr int umap(int f) {
-    if (FN == 0) return 0;
+    if (FN == 0 || FN == kFnTrace) return 0;
     if (FN == 1) return f;
     if (FN == 2) return pidx(f / 3, f % 3);
     return sort3_idx(f / 9, (f / 3) % 3, f % 3);
@@ -161,6 +171,8 @@ __device__ __forceinline__ void terms(const float *a, const float *c, float *t) 
             const int i = u2i(u, 0), j = u2i(u, 1);
             t[u] = a[i] * a[j] - c[pidx(i, j)];
         }
+    } else if constexpr (FN == kFnTrace) {
+        t[0] = (a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) - (c[0] + c[3] + c[5]);
     } else {
 #pragma unroll
         for (int u = 0; u < 10; ++u) {
@@ -199,6 +211,9 @@ __device__ __forceinline__ void phi_grads(const float *h, const float *a, const 
             e[pidx(i, k)] += h[u] * a[j];
             e[pidx(j, k)] += h[u] * a[i];
         }
+    } else if constexpr (FN == kFnTrace) {
+        for (int i = 0; i < 3; ++i) g[i] = 2.0f * h[0] * a[i];
+        e[0] = e[3] = e[5] = -h[0];
     }
 }
 
@@ -597,6 +612,10 @@ __device__ __forceinline__ void walk_candidates(const Hdr &h, const Bin &bin, co
             }
 }
 
+template <int FN, int CB>  // (with the _mc kernels, below)
+__device__ __forceinline__ void fwd_acc_c(int nch, const float *vr, float G, const float *a, const float *c,
+                                          float (*acc)[CB]);
+
 // The C > 1 forward (C = 1: k_vol_forward_m), CB channels per launch.  COUNT (diagnostic,
 // dgs_volume_count_pairs): instead of the outputs, counts[0] += the pairs evaluated (candidates
 // inside their cut box) and counts[1] += the live ones (G > 0).
@@ -644,6 +663,10 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
                     return;
                 }
                 if (!pair_eval(m, s, c, X, G, a)) return;
+                if constexpr (FN == kFnTrace) {  // no legacy bits to keep: the written-out sum (fwd_acc_c)
+                    fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc);
+                    return;
+                }
                 terms<FN>(a, c, t);
                 for (int ch = 0; ch < nch; ++ch) {
                     const float v = vr[ch];
@@ -734,6 +757,7 @@ __device__ __forceinline__ void bwd_pair(const float *m, const float *c, const f
 // three dimensions).  With the sample's h scaled to the full symmetric tensor H (h_u divided by
 // the multiplicity of its index set, at staging), phi = sum_u h_u t_u and its partials are
 //   laplacian: phi = a.(H a) - H:c,          g = 2 H a,          e = -H (packed, off-diagonals x2)
+//   trace    : phi = H (a.a - tr c),         g = 2 H a,          e = -H on the diagonal (H a scalar)
 //   third    : E_pq = H_pqk a_k, M = E a,     w_k = c_ij H_ijk,
 //              phi = 3 w.a - M.a,            g = 3 (w - M),      e = 3 E (off-diagonals x2)
 // and the pair only adds moments: G phi, G g, G phi X, G phi X X^T, G (g X^T + X g^T), G e.  The
@@ -771,6 +795,11 @@ __device__ __forceinline__ void phi_ge_t(const float *H, const float *a, const f
         phi = a[0] * ha0 + a[1] * ha1 + a[2] * ha2 - hc;
         g[0] = 2.0f * ha0; g[1] = 2.0f * ha1; g[2] = 2.0f * ha2;
         e[0] = -H[0]; e[1] = -2.0f * H[1]; e[2] = -2.0f * H[2]; e[3] = -H[3]; e[4] = -2.0f * H[4]; e[5] = -H[5];
+    } else if constexpr (FN == kFnTrace) {  // the laplacian's with H = H[0] I
+        phi = H[0] * ((a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) - (c2[0] + c2[3] + c2[5]));
+        const float h2 = 2.0f * H[0];
+        g[0] = h2 * a[0]; g[1] = h2 * a[1]; g[2] = h2 * a[2];
+        e[0] = -H[0]; e[3] = -H[0]; e[5] = -H[0];
     } else {
         // H000 H001 H002 H011 H012 H022 H111 H112 H122 H222 = H[0..9]
         const float E00 = H[0] * a[0] + H[1] * a[1] + H[2] * a[2];
@@ -827,7 +856,7 @@ __device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const
     if (!pair_eval(m, s, c, X, G, a)) return;
     float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     phi_ge_t<FN>(H, a, c2, phi, g, e);
-    vol_mom_add<FN>(G, phi, g, e, X, M);
+    vol_mom_add<mask_top(1 << FN)>(G, phi, g, e, X, M);
 }
 
 __device__ __forceinline__ void vol_mom_finish(const float *c, const VMom &M, float *dm, float *dc, float *dv) {
@@ -1040,7 +1069,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
 // a fused output equals the single call's by construction; the backward of one function is
 // k_vol_backward<FN, 1>, of several k_vol_backward_m.
 struct VOuts {
-    float *p[4];  // per function code; entries outside the mask unused
+    float *p[4];  // per function code (fn_slot: the trace in the laplacian's); entries outside the mask unused
 };
 
 // acc[u] += v G t_u for function FN: the definition of the C = 1 forward sum, with every rounding
@@ -1082,6 +1111,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                                                          const float *__restrict__ samples, VOuts outs) {
     constexpr int SKU = mask_ku(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
     __shared__ VCand<1> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1091,6 +1121,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
             if constexpr ((MASK & 2) != 0) fwd_nan<1>(outs.p[1], j);
             if constexpr ((MASK & 4) != 0) fwd_nan<2>(outs.p[2], j);
             if constexpr ((MASK & 8) != 0) fwd_nan<3>(outs.p[3], j);
+            if constexpr ((MASK & 16) != 0) fwd_nan<kFnTrace>(outs.p[S4], j);
         }
         return;
     }
@@ -1114,6 +1145,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 2) != 0) fwd_acc<1, BIG>(v, G, a, c, acc + O1);
                 if constexpr ((MASK & 4) != 0) fwd_acc<2, BIG>(v, G, a, c, acc + O2);
                 if constexpr ((MASK & 8) != 0) fwd_acc<3, BIG>(v, G, a, c, acc + O3);
+                if constexpr ((MASK & 16) != 0) fwd_acc<kFnTrace, BIG>(v, G, a, c, acc + O4);
             };
             walk_candidates<1>(
                 h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
@@ -1130,6 +1162,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 2) != 0) fwd_store<1>(outs.p[1], sid, acc + O1);
                 if constexpr ((MASK & 4) != 0) fwd_store<2>(outs.p[2], sid, acc + O2);
                 if constexpr ((MASK & 8) != 0) fwd_store<3>(outs.p[3], sid, acc + O3);
+                if constexpr ((MASK & 16) != 0) fwd_store<kFnTrace>(outs.p[S4], sid, acc + O4);
             }
         }
     }
@@ -1177,6 +1210,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                                           float *__restrict__ dvalues, float *__restrict__ dconics) {
     constexpr int SKU = mask_ku(MASK), TOP = mask_top(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
     __shared__ float4 scand[kWave];
     __shared__ float shrow[kWave][SKU];  // the candidates' H rows, function after function
     const Hdr &h = hdr_of(buf);  // (in place, as k_vol_forward_m)
@@ -1260,6 +1294,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                         if constexpr ((MASK & 2) != 0) stage_h<1>(&shrow[lane][O1], hrow + O1);
                                         if constexpr ((MASK & 4) != 0) stage_h<2>(&shrow[lane][O2], hrow + O2);
                                         if constexpr ((MASK & 8) != 0) stage_h<3>(&shrow[lane][O3], hrow + O3);
+                                        if constexpr ((MASK & 16) != 0) stage_h<kFnTrace>(&shrow[lane][O4], hrow + O4);
                                     }
                                     __syncthreads();
                                     const int cnt = min(kWave, e - q0);
@@ -1282,6 +1317,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                             if constexpr ((MASK & 2) != 0) phi_ge_add<1>(H + O1, a, c2, phi, gg, ee);
                                             if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, gg, ee);
                                             if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, gg, ee);
+                                            if constexpr ((MASK & 16) != 0) phi_ge_add<kFnTrace>(H + O4, a, c2, phi, gg, ee);
                                             vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
                                         }
                                 }
@@ -1331,6 +1367,8 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
                 bwd_pair<2, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
             if constexpr ((MASK & 8) != 0)
                 bwd_pair<3, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
+            if constexpr ((MASK & 16) != 0)
+                bwd_pair<kFnTrace, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnTrace), v, v + 3, v + 9);
         }
         for (int k = 0; k < NV; ++k)
             for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
@@ -1375,7 +1413,7 @@ __device__ __forceinline__ void sg_add(float w, float phi, const float *a, const
 }
 
 struct VDLs {
-    const float *p[4];  // dL/d out per function code; entries outside the mask unused
+    const float *p[4];  // dL/d out per function code (fn_slot); entries outside the mask unused
 };
 
 // C = 1, every mask
@@ -1388,6 +1426,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                                                        float *__restrict__ dsamples) {
     constexpr int SKU = mask_ku(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
+    constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
     __shared__ VCand<1> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1412,6 +1451,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 if constexpr ((MASK & 2) != 0) sg_load_h<1>(dLs.p[1], sid, H + O1);
                 if constexpr ((MASK & 4) != 0) sg_load_h<2>(dLs.p[2], sid, H + O2);
                 if constexpr ((MASK & 8) != 0) sg_load_h<3>(dLs.p[3], sid, H + O3);
+                if constexpr ((MASK & 16) != 0) sg_load_h<kFnTrace>(dLs.p[S4], sid, H + O4);
             }
             float ds[3] = {0.0f, 0.0f, 0.0f};
             auto eval = [&](const float *m, const float *c, float v) {
@@ -1423,6 +1463,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 if constexpr ((MASK & 2) != 0) phi_ge_add<1>(H + O1, a, c2, phi, g, e);
                 if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, g, e);
                 if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, g, e);
+                if constexpr ((MASK & 16) != 0) phi_ge_add<kFnTrace>(H + O4, a, c2, phi, g, e);
                 sg_add(v * G, phi, a, c, g, ds);
             };
             walk_candidates<1>(
@@ -1529,6 +1570,7 @@ __host__ __device__ __forceinline__ void for_mask(F f) {  // f(integral_constant
     if constexpr ((MASK & 2) != 0) f(std::integral_constant<int, 1>{});
     if constexpr ((MASK & 4) != 0) f(std::integral_constant<int, 2>{});
     if constexpr ((MASK & 8) != 0) f(std::integral_constant<int, 3>{});
+    if constexpr ((MASK & 16) != 0) f(std::integral_constant<int, kFnTrace>{});
 }
 
 // acc[u][ch] += v_ch G t_u for function FN with every rounding written out, so that an output does
@@ -1570,7 +1612,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict
             for_mask<MASK>([&](auto fc) {
                 constexpr int FN = decltype(fc)::value, K = VTr<FN>::K;
                 for (int f = 0; f < K; ++f)
-                    for (int ch = 0; ch < nch; ++ch) outs.p[FN][(j * K + f) * C + ch] = NAN;
+                    for (int ch = 0; ch < nch; ++ch) outs.p[fn_slot(FN)][(j * K + f) * C + ch] = NAN;
             });
         return;
     }
@@ -1610,7 +1652,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict
                 }
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value, K = VTr<FN>::K, O = mask_off(MASK, FN);
-                    float *__restrict__ out = outs.p[FN];
+                    float *__restrict__ out = outs.p[fn_slot(FN)];
 #pragma unroll
                     for (int f = 0; f < K; ++f)
 #pragma unroll
@@ -1877,7 +1919,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__
             if (active)
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value, KU = VTr<FN>::KU, K = VTr<FN>::K, O = mask_off(MASK, FN);
-                    const float *__restrict__ dL = dLs.p[FN];
+                    const float *__restrict__ dL = dLs.p[fn_slot(FN)];
 #pragma unroll
                     for (int f = 0; f < K; ++f)
 #pragma unroll
@@ -1932,11 +1974,20 @@ struct VArgs {  // what every launch takes
     hipStream_t s;
 };
 
+// The kernels' pointer structs from the caller's per-code arrays: four entries, or five (read only
+// when the mask holds the trace, whose pointer goes into its slot).
+template <int MASK, class S, class T>
+static S slots_of(T *const *ptrs) {
+    S o;
+    for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? ptrs[f] : nullptr;
+    if constexpr ((MASK & 16) != 0) o.p[fn_slot(kFnTrace)] = ptrs[kFnTrace];
+    return o;
+}
+
 // C = 1: every function mask
 template <int MASK>
 static void launch_fwd_m(const VArgs &a, float *const *outs) {
-    VOuts o;
-    for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? outs[f] : nullptr;
+    const VOuts o = slots_of<MASK, VOuts>(outs);
     k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, o);
 }
 template <int FN>
@@ -1951,6 +2002,7 @@ static void launch_bwd_m(const VArgs &a, const float *const *dLs, float *hs, flo
     launch_hsum_cat<1>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<2>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<3>(MASK, a.N, dLs, hs, a.s);
+    launch_hsum_cat<kFnTrace>(MASK, a.N, dLs, hs, a.s);
     k_vol_backward_m<MASK><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples,
                                                              hs, dm, dv, dc);
     k_vol_backward_big_m<MASK><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, hs,
@@ -1979,8 +2031,7 @@ static void launch_bwd(const VArgs &a, const float *dL, float *hs, float *dm, fl
 // sample gradients: every mask at C = 1; one function, 4 (C <= 4) or 8 channels per launch
 template <int MASK>
 static void launch_sgrad_m(const VArgs &a, const float *const *dLs, float *ds) {
-    VDLs d;
-    for (int f = 0; f < 4; ++f) d.p[f] = (MASK >> f) & 1 ? dLs[f] : nullptr;
+    const VDLs d = slots_of<MASK, VDLs>(dLs);
     k_vol_sgrad_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, d, ds);
 }
 template <int FN, int CB>
@@ -1994,8 +2045,7 @@ static void launch_sgrad(const VArgs &a, const float *dL, float *ds) {
 constexpr int kVolFusedCB = DGS_VOLUME_FUSED_MAX_C;
 template <int MASK>
 static void launch_fwd_mc(const VArgs &a, float *const *outs) {
-    VOuts o;
-    for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? outs[f] : nullptr;
+    const VOuts o = slots_of<MASK, VOuts>(outs);
     k_vol_forward_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
                                                                           a.conics, a.samples, o);
 }
@@ -2014,8 +2064,7 @@ static void launch_bwd_mc(const VArgs &a, const float *const *dLs, float *hs, fl
 }
 template <int MASK>
 static void launch_sgrad_mc(const VArgs &a, const float *const *dLs, float *ds) {
-    VDLs d;
-    for (int f = 0; f < 4; ++f) d.p[f] = (MASK >> f) & 1 ? dLs[f] : nullptr;
+    const VDLs d = slots_of<MASK, VDLs>(dLs);
     k_vol_sgrad_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
                                                                         a.conics, a.samples, d, ds);
 }
@@ -2029,6 +2078,9 @@ static int fn_cb_case(int mask, int C) { return mask_top(mask) * 3 + (C <= 1 ? 0
 #define DGS_VOL_FN_C1(X) X(0, 1) X(1, 1) X(2, 1) X(3, 1)
 #define DGS_VOL_FN_CB(X) X(0, 4) X(0, 8) X(1, 4) X(1, 8) X(2, 4) X(2, 8) X(3, 4) X(3, 8)
 #define DGS_VOL_FN_CB_CASE(FN, CB) FN * 3 + (CB == 1 ? 0 : CB == 4 ? 1 : 2)
+// the masks with the trace (dgs_volume_*_ops): alone, and with a non-empty subset of {0, 1, 3}
+#define DGS_VOL_MASKS_TRACE_FUSED(X) X(17) X(18) X(19) X(24) X(25) X(26) X(27)
+#define DGS_VOL_MASKS_TRACE(X) X(16) DGS_VOL_MASKS_TRACE_FUSED(X)
 
 }  // namespace vol
 }  // namespace dgs
@@ -2443,6 +2495,150 @@ extern "C" int dgs_volume_backward_samples_fused(int mask, int P, int N, int C, 
 #define X(M) case M: launch_sgrad_mc<M>(a, dL_douts, dL_dsamples); break;
         DGS_VOL_MASKS_FUSED(X)
 #undef X
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+// ---- the *_ops entries: the *_fused entries plus function 4, the trace of the laplacian (bit 4).  A
+// mask below 16 is the *_fused entry itself; the trace alone runs at any C (C = 1: the mask kernels,
+// C > 1: the per-function kernels in channel blocks of 4 / 8); the trace with others of {0, 1, 3}
+// takes the mask kernels at C = 1 and the _mc kernels at 2 <= C <= DGS_VOLUME_FUSED_MAX_C.
+static bool ops_mask_ok(int mask) { return mask >= 1 && mask <= 31 && !((mask & 4) && (mask & 16)); }
+static int vol_check_ops(int mask, int P, int N, int C, const void *binning, size_t bytes) {
+    if (!ops_mask_ok(mask))
+        return fail(DGS_ERR_ARG, "dgs_volume_*_ops: mask must be 1..31 without both the laplacian (4) and its trace (16)");
+    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
+    if (mask != 16 && C > DGS_VOLUME_FUSED_MAX_C)
+        return fail(DGS_ERR_ARG, "dgs_volume_*_ops: several functions need C <= 4 (DGS_VOLUME_FUSED_MAX_C); "
+                                 "call them per function and add");
+    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+    return DGS_OK;
+}
+
+extern "C" size_t dgs_volume_workspace_size_ops(int mask, int P, int N, int C, int backward) {
+    if (!ops_mask_ok(mask)) return 0;
+    if (mask < 16) return dgs_volume_workspace_size_fused(mask, P, N, C, backward);
+    if (!backward || N <= 0 || C <= 0 || (mask != 16 && C > DGS_VOLUME_FUSED_MAX_C)) return 0;
+    return (size_t)N * mask_ku(mask) * C * 4;  // hs[N][unique components of the mask][C]
+}
+
+extern "C" int dgs_volume_forward_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                                      const float *conics, const float *samples, const void *binning,
+                                      size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug) {
+    if (ops_mask_ok(mask) && mask < 16)
+        return dgs_volume_forward_fused(mask, P, N, C, means, values, conics, samples, binning, binning_bytes, outs,
+                                        stream, debug);
+    if (int rc = vol_check_ops(mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_ops: outs required");
+    if (N == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_fwd_m<M>(a, outs); break;
+            DGS_VOL_MASKS_TRACE(X)
+#undef X
+        }
+    } else if (mask == 16) {
+        if (C <= 4) launch_fwd<kFnTrace, 4>(a, outs[kFnTrace]);
+        else launch_fwd<kFnTrace, 8>(a, outs[kFnTrace]);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_fwd_mc<M>(a, outs); break;
+            DGS_VOL_MASKS_TRACE_FUSED(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                                       const float *conics, const float *samples, const float *const *dL_douts,
+                                       const void *binning, size_t binning_bytes, float *dL_dmeans,
+                                       float *dL_dvalues, float *dL_dconics, void *workspace,
+                                       size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    if (ops_mask_ok(mask) && mask < 16)
+        return dgs_volume_backward_fused(mask, P, N, C, means, values, conics, samples, dL_douts, binning,
+                                         binning_bytes, dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes,
+                                         stream, debug);
+    if (int rc = vol_check_ops(mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_ops: dL_douts required");
+    if (workspace_bytes < dgs_volume_workspace_size_ops(mask, P, N, C, 1) || (N > 0 && P > 0 && !workspace))
+        return fail(DGS_ERR_ARG, "dgs_volume_backward_ops: workspace missing or too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) return DGS_OK;
+    if (N == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * C * 4, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
+        return DGS_OK;
+    }
+    for (int f = 0; f < 5; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_ops: a dL_dout of the mask is NULL");
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    float *hs = static_cast<float *>(workspace);
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_bwd_m<M>(a, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics); break;
+            DGS_VOL_MASKS_TRACE(X)
+#undef X
+        }
+    } else if (mask == 16) {
+        if (C <= 4) launch_bwd<kFnTrace, 4>(a, dL_douts[kFnTrace], hs, dL_dmeans, dL_dvalues, dL_dconics);
+        else launch_bwd<kFnTrace, 8>(a, dL_douts[kFnTrace], hs, dL_dmeans, dL_dvalues, dL_dconics);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_bwd_mc<M>(a, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics); break;
+            DGS_VOL_MASKS_TRACE_FUSED(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_samples_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                                               const float *conics, const float *samples,
+                                               const float *const *dL_douts, const void *binning,
+                                               size_t binning_bytes, float *dL_dsamples, void *workspace,
+                                               size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    if (ops_mask_ok(mask) && mask < 16)
+        return dgs_volume_backward_samples_fused(mask, P, N, C, means, values, conics, samples, dL_douts, binning,
+                                                 binning_bytes, dL_dsamples, workspace, workspace_bytes, stream, debug);
+    if (int rc = vol_check_ops(mask, P, N, C, binning, binning_bytes)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_ops: dL_douts required");
+    if (N == 0) return DGS_OK;
+    if (!dL_dsamples) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_ops: dL_dsamples required");
+    for (int f = 0; f < 5; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_ops: a dL_dout of the mask is NULL");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dsamples, 0, (size_t)N * 12, s));
+        return DGS_OK;
+    }
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_sgrad_m<M>(a, dL_douts, dL_dsamples); break;
+            DGS_VOL_MASKS_TRACE(X)
+#undef X
+        }
+    } else if (mask == 16) {
+        if (C <= 4) launch_sgrad<kFnTrace, 4>(a, dL_douts[kFnTrace], dL_dsamples);
+        else launch_sgrad<kFnTrace, 8>(a, dL_douts[kFnTrace], dL_dsamples);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_sgrad_mc<M>(a, dL_douts, dL_dsamples); break;
+            DGS_VOL_MASKS_TRACE_FUSED(X)
+#undef X
+        }
     }
     DGS_LAUNCH_CHECK(s, debug);
     return DGS_OK;

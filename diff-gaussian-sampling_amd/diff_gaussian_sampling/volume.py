@@ -29,7 +29,17 @@ import torch
 
 from . import _C, call_debug
 
-FUNCTION_CODES = {"gaussian": 0, "derivative": 1, "laplacian": 2, "third": 3}
+FUNCTION_CODES = {"gaussian": 0, "derivative": 1, "laplacian": 2, "third": 3, "laplacian_trace": 4}
+TRACE = FUNCTION_CODES["laplacian_trace"]
+
+
+def _multi_calls(codes):
+    """The forward, backward and sample-gradient bindings of a list of codes: the _ops ones
+    (dgs_volume_*_ops, five functions) only when the trace is among them, else the ones every
+    call without it has always taken."""
+    if TRACE in codes:
+        return _C.volume_forward_ops, _C.volume_backward_ops, _C.volume_samples_backward_ops
+    return _C.volume_forward_multi, _C.volume_backward_multi, _C.volume_samples_backward
 
 
 def preprocess_volume(means, conics, samples, debug=False):
@@ -84,11 +94,16 @@ class _SampleVolumeSG(torch.autograd.Function):
 
 
 def sample_volume(function, means, values, conics, samples, binning, debug=False, sample_grad=False):
-    """One of the four functions ("gaussian", "derivative", "laplacian", "third" or 0..3) of a
-    D = 3 field at `samples`, through the binning of preprocess_volume.  sample_grad=True also
+    """One of the five functions ("gaussian", "derivative", "laplacian", "third",
+    "laplacian_trace" or 0..4) of a D = 3 field at `samples`, through the binning of
+    preprocess_volume.  "laplacian_trace" is the trace of the laplacian, [N, C]: what a diffusion,
+    Poisson, wave or Navier-Stokes residual uses of the [N, 3, 3, C] Hessian, at about the
+    gaussian's cost ("Trace Laplacian").  sample_grad=True also
     returns the gradient of `samples` when they require one (one more walk of the candidates, about
     a forward's time; without the flag such samples raise NotImplementedError)."""
     code = FUNCTION_CODES[function] if isinstance(function, str) else int(function)
+    if code == TRACE:  # (the per-function bindings keep refusing it: the _ops ones take it)
+        return sample_volume_multi((code,), means, values, conics, samples, binning, debug, sample_grad)[0]
     fn = _SampleVolumeSG if sample_grad else _SampleVolume
     return fn.apply(code, means, values, conics, samples, binning, debug)
 
@@ -99,7 +114,7 @@ class _SampleVolumeMulti(torch.autograd.Function):
         if ctx.needs_input_grad[4]:
             raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them "
                                       "(or ask for it: sample_grad=True)")
-        outs = call_debug(_C.volume_forward_multi, debug, "vol_multi_fw", list(codes), means, values, conics,
+        outs = call_debug(_multi_calls(codes)[0], debug, "vol_multi_fw", list(codes), means, values, conics,
                           samples, binning, debug)
         ctx.codes, ctx.debug = codes, debug
         ctx.save_for_backward(means, values, conics, samples, binning)
@@ -111,7 +126,8 @@ class _SampleVolumeMulti(torch.autograd.Function):
         live = [(c, g.contiguous()) for c, g in zip(ctx.codes, grads) if g is not None]
         if not live:
             return (None,) * 7
-        gm, gv, gc = call_debug(_C.volume_backward_multi, ctx.debug, "vol_multi_bw", [c for c, _ in live],
+        live_codes = [c for c, _ in live]
+        gm, gv, gc = call_debug(_multi_calls(live_codes)[1], ctx.debug, "vol_multi_bw", live_codes,
                                 means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
         return None, gm, gv, gc, None, None, None
 
@@ -122,7 +138,7 @@ class _SampleVolumeMultiSG(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, codes, means, values, conics, samples, binning, debug):
-        outs = call_debug(_C.volume_forward_multi, debug, "vol_multi_fw", list(codes), means, values, conics,
+        outs = call_debug(_multi_calls(codes)[0], debug, "vol_multi_fw", list(codes), means, values, conics,
                           samples, binning, debug)
         ctx.codes, ctx.debug = codes, debug
         ctx.save_for_backward(means, values, conics, samples, binning)
@@ -135,18 +151,22 @@ class _SampleVolumeMultiSG(torch.autograd.Function):
         if not live:
             return (None,) * 7
         gm = gv = gc = gs = None
+        live_codes = [c for c, _ in live]
+        _, bwd, sgrad = _multi_calls(live_codes)
         if any(ctx.needs_input_grad[1:4]):
-            gm, gv, gc = call_debug(_C.volume_backward_multi, ctx.debug, "vol_multi_bw", [c for c, _ in live],
+            gm, gv, gc = call_debug(bwd, ctx.debug, "vol_multi_bw", live_codes,
                                     means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
         if ctx.needs_input_grad[4]:
-            gs = call_debug(_C.volume_samples_backward, ctx.debug, "vol_multi_sg", [c for c, _ in live], means,
+            gs = call_debug(sgrad, ctx.debug, "vol_multi_sg", live_codes, means,
                             values, conics, samples, [g for _, g in live], binning, ctx.debug)
         return None, gm, gv, gc, gs, None, None
 
 
 def sample_volume_multi(functions, means, values, conics, samples, binning, debug=False, sample_grad=False):
-    """Several of the four functions (distinct names or codes) of a D = 3 field at `samples`;
-    returns their outputs in the order asked.  Up to C = 4 (a velocity field, velocity and pressure)
+    """Several of the five functions (distinct names or codes) of a D = 3 field at `samples`;
+    returns their outputs in the order asked.  With "laplacian_trace" among them the call goes
+    through dgs_volume_*_ops; asked together with "laplacian", the trace runs as its own call
+    beside the fused rest.  Up to C = 4 (a velocity field, velocity and pressure)
     they share one walk of the candidates, forward and backward (include/dgs_volume.h,
     dgs_volume_*_multi at C = 1, dgs_volume_*_fused at C = 2..4); with more channels the
     per-function kernels run in turn and their gradients are added.  Each output is bitwise the one
@@ -204,7 +224,7 @@ class VolumeSampler:
                              self.debug, self.sample_grad)
 
     def sample_gaussians_multi(self, *functions):
-        """Several functions ("gaussian", "derivative", "laplacian", "third" or 0..3) in one
+        """Several functions ("gaussian", "derivative", "laplacian", "third", "laplacian_trace" or 0..4) in one
         call; returns a tuple in the order asked (sample_volume_multi: one walk of the candidates
         for fields of up to four channels)."""
         self._rebin_if_changed()
@@ -222,3 +242,7 @@ class VolumeSampler:
 
     def sample_gaussians_third_derivative(self):
         return self._run(3)
+
+    def sample_gaussians_laplacian_trace(self):
+        """The trace of the laplacian, [N, C] (one value per channel)."""
+        return self._run(TRACE)

@@ -137,6 +137,47 @@ int dgs_volume_backward_samples_fused(int mask, int P, int N, int C, const float
                                       const void *binning, size_t binning_bytes, float *dL_dsamples,
                                       void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
 
+/* A fifth function, the trace of the laplacian (what diffusion, Poisson, wave and Navier-Stokes
+ * residuals use of the Hessian; DESIGN.md §4.8, "Trace Laplacian"): code 4, bit 4 of a mask,
+ *   out[N][C],  out[n][ch] = sum_g v_g,ch G t,   t = (a0 a0 + a1 a1 + a2 a2) - (c00 + c11 + c22),
+ * t evaluated in fp32 in exactly that order without contraction, over the pair set, wrap and
+ * exact-zero skip of the other four.  In the gradients it is the laplacian with the sample's
+ * tensor H = h I: phi = h t, d phi / d a = 2 h a, d phi / d c = -h on the three diagonal entries.
+ * It rounds differently from the sum of the laplacian's three diagonal outputs and is not bitwise
+ * that sum.  The forward sum is written out: among the binned Gaussians fma(round(v G), t, acc);
+ * among the others round(acc + round(round(v G) t)) at C = 1 and the same fma at C > 1.  So an
+ * output of a mask with the trace is bit-identical to the mask-16 call's at the same C.
+ *
+ * The *_ops entries take the argument lists of the *_fused entries with outs / dL_douts arrays of
+ * FIVE pointers (indexed by function code; entries outside the mask ignored).  Valid masks are
+ * 1..31 without both bit 2 and bit 4 (the laplacian already holds its trace); DGS_ERR_ARG otherwise.
+ *   - mask < 16: the call is the *_fused entry itself (the same checks, the same launches,
+ *     bit-identical results; the fifth pointer is not read);
+ *   - mask 16: any C (C > 1 in channel blocks of 4 and 8, as the gaussian);
+ *   - the trace with some of functions 0, 1, 3 (masks 17, 18, 19, 24, 25, 26, 27): one walk of the
+ *     candidates at 1 <= C <= DGS_VOLUME_FUSED_MAX_C; above it DGS_ERR_ARG (call per function and
+ *     add) and a workspace size of 0.
+ * Backward workspace: N * (unique components of the mask, 1 for the trace) * C * 4 bytes; the
+ * forward and the sample gradient need none.  Edge sizes, the stale buffer / changed input guard
+ * (NaN in every output of the mask, every gradient and dL_dsamples), DGS_ERR_BUFFER for a missing
+ * or short binning and the ordering of calls on one binning are those of the *_fused calls; no
+ * host sync, no allocation.  New exported functions only: DGS_ABI_VERSION is unchanged, and the
+ * entries above keep refusing bit 4. */
+#define DGS_VOLUME_FN_LAPLACIAN_TRACE 4
+size_t dgs_volume_workspace_size_ops(int mask, int P, int N, int C, int backward);
+int dgs_volume_forward_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                           const float *conics, const float *samples, const void *binning,
+                           size_t binning_bytes, float *const *outs, dgs_stream_t stream, int debug);
+int dgs_volume_backward_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                            const float *conics, const float *samples, const float *const *dL_douts,
+                            const void *binning, size_t binning_bytes, float *dL_dmeans,
+                            float *dL_dvalues, float *dL_dconics, void *workspace,
+                            size_t workspace_bytes, dgs_stream_t stream, int debug);
+int dgs_volume_backward_samples_ops(int mask, int P, int N, int C, const float *means, const float *values,
+                                    const float *conics, const float *samples, const float *const *dL_douts,
+                                    const void *binning, size_t binning_bytes, float *dL_dsamples,
+                                    void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
+
 /* Diagnostic (not on any reference API): counts[0] = pairs the forward evaluates (candidates
  * inside their own cut box), counts[1] = live pairs (G = expf(power) > 0).  Host, syncs;
  * DGS_ERR_BUFFER when the inputs differ from the binned ones. */

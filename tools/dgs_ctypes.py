@@ -336,18 +336,43 @@ for _n in ("dgs_volume_backward_samples_fused", "dgs_volume_backward_samples"):
     getattr(_lib, _n).argtypes = [_I] * 4 + [_P] * 4 + [_PP, _P, _SZ, _P, _P, _SZ, _P, _I]
 
 
+# the *_ops entries (five functions: code 4 is the trace of the laplacian, [N, C]): entry="ops"
+_PP5 = ctypes.c_void_p * 5
+_lib.dgs_volume_workspace_size_ops.restype = _SZ
+_lib.dgs_volume_workspace_size_ops.argtypes = [_I] * 5
+_lib.dgs_volume_forward_ops.argtypes = [_I] * 4 + [_P] * 4 + [_P, _SZ, _PP5, _P, _I]
+_lib.dgs_volume_backward_ops.argtypes = [_I] * 4 + [_P] * 4 + [_PP5, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _I]
+_lib.dgs_volume_backward_samples_ops.argtypes = [_I] * 4 + [_P] * 4 + [_PP5, _P, _SZ, _P, _P, _SZ, _P, _I]
+VOLUME_TRACE = 4
+
+
+def _vol_ptrs(entry, by_code):
+    """the per-code pointer array of an entry: five for "ops", else four"""
+    n, T = (5, _PP5) if entry == "ops" else (4, _PP)
+    return T(*[by_code[c].data_ptr() if c in by_code else None for c in range(n)])
+
+
+def _vol_shape(N, c, C):
+    return (N, C) if c == VOLUME_TRACE else (N,) + (3,) * c + (C,)
+
+
 def volume_workspace_size_fused(mask, P, N, C, backward):
     return _lib.dgs_volume_workspace_size_fused(mask, P, N, C, backward)
 
 
+def volume_workspace_size_ops(mask, P, N, C, backward):
+    return _lib.dgs_volume_workspace_size_ops(mask, P, N, C, backward)
+
+
 def volume_forward_fused(codes, means, values, conics, samples, binning, debug, entry="fused"):
     """Outputs [N, 3^f, C] of the functions `codes` (0..3, each once) in the order given.
-    entry="multi" calls dgs_volume_forward_multi instead (several functions: C = 1 only)."""
+    entry="multi" calls dgs_volume_forward_multi instead (several functions: C = 1 only), entry="ops"
+    dgs_volume_forward_ops (codes 0..4; code 4, the trace of the laplacian, is [N, C])."""
     means, values, conics, samples = map(_f32, (means, values, conics, samples))
     P, N, C = means.shape[0], samples.shape[0], values.shape[1]
     mask = sum(1 << c for c in codes)
-    outs = {c: torch.zeros((N,) + (3,) * c + (C,), device=means.device) for c in codes}
-    ptrs = _PP(*[outs[c].data_ptr() if c in outs else None for c in range(4)])
+    outs = {c: torch.zeros(_vol_shape(N, c, C), device=means.device) for c in codes}
+    ptrs = _vol_ptrs(entry, outs)
     _check(getattr(_lib, "dgs_volume_forward_" + entry)(
         mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), _ptr(binning), binning.numel(), ptrs,
         _stream(), int(bool(debug))))
@@ -362,7 +387,7 @@ def volume_backward_fused(codes, means, values, conics, samples, dLs, binning, d
     P, N, C = means.shape[0], samples.shape[0], values.shape[1]
     mask = sum(1 << c for c in codes)
     dm, dv, dc = (torch.zeros(P, k, device=means.device) for k in (3, C, 6))
-    ptrs = _PP(*[dLs[c].data_ptr() if c in dLs else None for c in range(4)])
+    ptrs = _vol_ptrs(entry, dLs)
     if workspace is None:
         size = getattr(_lib, "dgs_volume_workspace_size_" + entry)(mask, P, N, C, 1)
         workspace = torch.empty(size, dtype=torch.uint8, device=means.device)
@@ -379,8 +404,9 @@ def volume_samples_backward_fused(codes, means, values, conics, samples, dLs, bi
     P, N, C = means.shape[0], samples.shape[0], values.shape[1]
     mask = sum(1 << c for c in codes)
     ds = torch.zeros(N, 3, device=means.device)
-    ptrs = _PP(*[dLs[c].data_ptr() if c in dLs else None for c in range(4)])
-    fn = _lib.dgs_volume_backward_samples_fused if entry == "fused" else _lib.dgs_volume_backward_samples
+    ptrs = _vol_ptrs(entry, dLs)
+    fn = {"fused": _lib.dgs_volume_backward_samples_fused, "ops": _lib.dgs_volume_backward_samples_ops,
+          "multi": _lib.dgs_volume_backward_samples}[entry]
     _check(fn(mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
               binning.numel(), _ptr(ds), None, 0, _stream(), int(bool(debug))))
     return ds

@@ -1,7 +1,7 @@
 """Times the fused D = 3 multi-function call against the per-function calls on one binning.
 
     python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
-                                       [--rounds 3] [--steps 3] [--C 3] [--separate-only]
+                                       [--rounds 3] [--steps 3] [--C 3] [--separate-only] [--trace-vs-hessian]
 
 The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice; C = 1 unless --C).  After settle
 steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
@@ -13,6 +13,12 @@ and `fused_over_last`, the fused step against the most expensive (last named) fu
 runs through tools/ab.py --script); --C sets the channel count (the fused call shares one walk up
 to C = 4; with more channels, or in a package from before that, it is the per-function calls added:
 the yardstick of an A/B run through tools/ab.py --script against a build of the parent commit).
+
+--trace-vs-hessian (with "laplacian_trace" among --functions): instead of fused against separate,
+times in alternation the call as given (`fused_ms`, also `trace_ms`) against what a user without the
+trace does (`separate_ms`, also `hessian_ms`): the same call with "laplacian" in its place, followed
+by `out.diagonal(dim1=1, dim2=2).sum(-1)`; both are forward + backward from the same upstream
+gradients.  `single_ms` then holds the other functions' single calls and the laplacian's.
 """
 import argparse
 import json
@@ -39,6 +45,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--settle", type=int, default=2)
     ap.add_argument("--separate-only", action="store_true")
+    ap.add_argument("--trace-vs-hessian", action="store_true")
     ap.add_argument("--C", type=int, default=1, help="channels")
     args = ap.parse_args()
     C = args.C
@@ -52,9 +59,14 @@ def main():
     vs = VolumeSampler(False)
     vs.preprocess(means, values, covs, conics, samples)
     gen = torch.Generator().manual_seed(5)
-    w = {f: torch.randn((N,) + (3,) * FUNCTION_CODES[f] + (C,), generator=gen).to(dev) for f in fns}
+    order = {"laplacian_trace": 0}  # (its output is [N, C])
+    w = {f: torch.randn((N,) + (3,) * order.get(f, FUNCTION_CODES[f]) + (C,), generator=gen).to(dev) for f in fns}
     single = {"gaussian": vs.sample_gaussians, "derivative": vs.sample_gaussians_derivative,
               "laplacian": vs.sample_gaussians_laplacian, "third": vs.sample_gaussians_third_derivative}
+    if "laplacian_trace" in fns:
+        single["laplacian_trace"] = vs.sample_gaussians_laplacian_trace
+    if args.trace_vs_hessian:
+        return trace_vs_hessian(args, vs, fns, w, single, (means, values, conics), N)
 
     def step(which):
         for t in (means, values, conics):
@@ -90,6 +102,48 @@ def main():
         res.update(fused_ms=med["fused"], fused_rounds_ms=times["fused"], speedup=med["separate"] / med["fused"],
                    fused_over_last=med["fused"] / med[fns[-1]])
     print(json.dumps(res), flush=True)
+
+
+def trace_vs_hessian(args, vs, fns, w, single, params, N):
+    assert "laplacian_trace" in fns and "laplacian" not in fns, "--functions must hold laplacian_trace, not laplacian"
+    hfns = ["laplacian" if f == "laplacian_trace" else f for f in fns]
+    others = [f for f in fns if f != "laplacian_trace"] + ["laplacian"]
+
+    def step(which):
+        for t in params:
+            t.grad = None
+        if which == "trace":
+            outs = vs.sample_gaussians_multi(*fns) if len(fns) > 1 else (single[fns[0]](),)
+        elif which == "hessian":
+            outs = vs.sample_gaussians_multi(*hfns) if len(fns) > 1 else (single["laplacian"](),)
+            outs = [o.diagonal(dim1=1, dim2=2).sum(-1) if f == "laplacian" else o for f, o in zip(hfns, outs)]
+        else:  # a single function, as the main mode times it
+            o = single[which]()
+            return o.backward(torch.ones_like(o) if which == "laplacian" else w[which])
+        torch.autograd.backward(list(outs), [w[f] for f in fns])
+
+    def timed(which):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(which)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+
+    kinds = ["trace", "hessian"]
+    for k in kinds:
+        for _ in range(args.settle):
+            step(k)
+    times = {k: [] for k in kinds + others}
+    for _ in range(args.rounds):
+        for k in kinds + others:
+            times[k].append(timed(k))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps({"P": args.P, "N": N, "C": args.C, "grid3": args.grid3, "functions": fns, "mode": "trace-vs-hessian",
+                      "rounds": args.rounds, "steps": args.steps, "trace_ms": med["trace"], "hessian_ms": med["hessian"],
+                      "fused_ms": med["trace"], "separate_ms": med["hessian"], "speedup": med["hessian"] / med["trace"],
+                      "trace_rounds_ms": times["trace"], "hessian_rounds_ms": times["hessian"],
+                      "single_ms": {f: med[f] for f in others}}), flush=True)
 
 
 if __name__ == "__main__":
