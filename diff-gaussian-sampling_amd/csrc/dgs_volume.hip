@@ -32,6 +32,11 @@
 //   * a fifth function, the trace of the laplacian (code 4, bit 4 of a mask, one component per
 //     channel; the dgs_volume_*_ops entries): new instantiations of the same templates, alone at any
 //     C and fused with functions 0, 1, 3 up to C = 4 ("Trace Laplacian").
+//   * a sixth function, a constant-coefficient linear operator c0 u + b.grad u + W:hess u (code 5,
+//     bit 5, one component per channel; the dgs_volume_*_linop entries): again new instantiations,
+//     alone at any C and fused with functions 0, 1 up to C = 4.  Its ten coefficients are a trailing
+//     by-value kernel argument (VCoef) that only these instantiations have ("Linear
+//     operator").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,26 +101,57 @@ __host__ __device__ constexpr int sort3_idx(int i, int j, int k) {
 // Function 4 (bit 4) is the trace of the laplacian, one component ("Trace
 // Laplacian"); it comes last in a concatenated row and never shares a mask with the laplacian.
 __host__ __device__ constexpr int mask_ku(int mask) {
-    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0) + (mask & 16 ? 1 : 0);
+    return (mask & 1 ? 1 : 0) + (mask & 2 ? 3 : 0) + (mask & 4 ? 6 : 0) + (mask & 8 ? 10 : 0) + (mask & 16 ? 1 : 0) +
+           (mask & 32 ? 1 : 0);
 }
 // offset of function f's unique components in a concatenated row of the mask's functions
 __host__ __device__ constexpr int mask_off(int mask, int f) { return mask_ku(mask & ((1 << f) - 1)); }
 // the order of the mask's highest function (the trace is of order 2: vol_mom_add<TOP>)
-__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & (4 | 16) ? 2 : mask & 2 ? 1 : 0; }
+__host__ __device__ constexpr int mask_top(int mask) { return mask & 8 ? 3 : mask & (4 | 16 | 32) ? 2 : mask & 2 ? 1 : 0; }
 constexpr int kFnTrace = DGS_VOLUME_FN_LAPLACIAN_TRACE;
-// The kernels' pointer structs (VOuts, VDLs) have one slot per function code 0..3; the trace takes
-// the laplacian's, which a mask with the trace never uses.
-__host__ __device__ constexpr int fn_slot(int fn) { return fn == kFnTrace ? 2 : fn; }
+// Function 5 (bit 5) is the linear operator, one component like the trace ("Linear
+// operator"); it comes last in a row and shares a mask only with the gaussian and the derivative.
+constexpr int kFnOp = DGS_VOLUME_FN_OPERATOR;
+// The kernels' pointer structs (VOuts, VDLs) have one slot per function code 0..3; the trace and the
+// operator take the laplacian's, which a mask with either never uses.
+__host__ __device__ constexpr int fn_slot(int fn) { return fn == kFnTrace || fn == kFnOp ? 2 : fn; }
+
+// The operator's coefficients as the kernels take them, by value (wave-uniform: scalar registers):
+// k = [c0, b0, b1, b2, w00, 2 w01, 2 w02, w11, 2 w12, w22], the doubling done on the host (exact).
+// Only the instantiations with the operator have this argument (the kernels' trailing pack CF is
+// empty for every other one, so their argument lists are what they were).
+struct VCoef {
+    float k[10];
+};
+__device__ __forceinline__ const float *coef_of() { return nullptr; }
+__device__ __forceinline__ const float *coef_of(const VCoef &cf) { return cf.k; }
+// The operator's per-pair factor t (include/dgs_volume.h: the order of the roundings), from the
+// packed conic c; half: 0.5 where c holds the off-diagonals doubled (c2 of the moment form; exact).
+__device__ __forceinline__ float op_t(const float *a, const float *c, const float *k, float half = 1.0f) {
+    DGS_NO_CONTRACT
+    const float lin = k[1] * a[0] + k[2] * a[1] + k[3] * a[2];
+    const float q = k[4] * (a[0] * a[0] - c[0]) + k[5] * (a[0] * a[1] - half * c[1]) +
+                    k[6] * (a[0] * a[2] - half * c[2]) + k[7] * (a[1] * a[1] - c[3]) +
+                    k[8] * (a[1] * a[2] - half * c[4]) + k[9] * (a[2] * a[2] - c[5]);
+    return (k[0] + lin) + q;
+}
+// g = d(h t)/da = h (b + 2 W a) and e = d(h t)/dc = -h k_u (packed)
+__device__ __forceinline__ void op_ge(float h, const float *a, const float *k, float *g, float *e) {
+    g[0] = h * (k[1] + (2.0f * k[4] * a[0] + k[5] * a[1] + k[6] * a[2]));
+    g[1] = h * (k[2] + (k[5] * a[0] + 2.0f * k[7] * a[1] + k[8] * a[2]));
+    g[2] = h * (k[3] + (k[6] * a[0] + k[8] * a[1] + 2.0f * k[9] * a[2]));
+    for (int q = 0; q < 6; ++q) e[q] = -h * k[4 + q];
+}
 
 template <int FN>
 struct VTr {
-    static constexpr int KU = mask_ku(1 << FN), K = FN == 0 || FN == kFnTrace ? 1 : FN == 1 ? 3 : FN == 2 ? 9 : 27;
+    static constexpr int KU = mask_ku(1 << FN), K = FN == 0 || FN == kFnTrace || FN == kFnOp ? 1 : FN == 1 ? 3 : FN == 2 ? 9 : 27;
 };
 
 // unique component of the full output index f (row-major over the 3^FN indices)
 template <int FN>
 __host__ __device__ constexpr int umap(int f) {
-    if (FN == 0 || FN == kFnTrace) return 0;
+    if (FN == 0 || FN == kFnTrace || FN == kFnOp) return 0;
     if (FN == 1) return f;
     if (FN == 2) return pidx(f / 3, f % 3);
     return sort3_idx(f / 9, (f / 3) % 3, f % 3);
@@ -159,7 +195,7 @@ __device__ __forceinline__ bool pair_eval(const float *m, const float *s, const 
 }
 
 template <int FN>
-__device__ __forceinline__ void terms(const float *a, const float *c, float *t) {
+__device__ __forceinline__ void terms(const float *a, const float *c, float *t, const float *cf = nullptr) {
     DGS_NO_CONTRACT
     if constexpr (FN == 0) {
         t[0] = 1.0f;
@@ -173,6 +209,8 @@ __device__ __forceinline__ void terms(const float *a, const float *c, float *t) 
         }
     } else if constexpr (FN == kFnTrace) {
         t[0] = (a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) - (c[0] + c[3] + c[5]);
+    } else if constexpr (FN == kFnOp) {
+        t[0] = op_t(a, c, cf);
     } else {
 #pragma unroll
         for (int u = 0; u < 10; ++u) {
@@ -184,7 +222,8 @@ __device__ __forceinline__ void terms(const float *a, const float *c, float *t) 
 
 // g = d phi / d a and e = d phi / d c (explicit, packed conic) for phi = sum_u h_u t_u.
 template <int FN>
-__device__ __forceinline__ void phi_grads(const float *h, const float *a, const float *c, float *g, float *e) {
+__device__ __forceinline__ void phi_grads(const float *h, const float *a, const float *c, float *g, float *e,
+                                          const float *cf = nullptr) {
     for (int i = 0; i < 3; ++i) g[i] = 0.0f;
     for (int q = 0; q < 6; ++q) e[q] = 0.0f;
     if constexpr (FN == 1) {
@@ -214,6 +253,8 @@ __device__ __forceinline__ void phi_grads(const float *h, const float *a, const 
     } else if constexpr (FN == kFnTrace) {
         for (int i = 0; i < 3; ++i) g[i] = 2.0f * h[0] * a[i];
         e[0] = e[3] = e[5] = -h[0];
+    } else if constexpr (FN == kFnOp) {
+        op_ge(h[0], a, cf, g, e);
     }
 }
 
@@ -614,19 +655,22 @@ __device__ __forceinline__ void walk_candidates(const Hdr &h, const Bin &bin, co
 
 template <int FN, int CB>  // (with the _mc kernels, below)
 __device__ __forceinline__ void fwd_acc_c(int nch, const float *vr, float G, const float *a, const float *c,
-                                          float (*acc)[CB]);
+                                          float (*acc)[CB], const float *cf = nullptr);
 
 // The C > 1 forward (C = 1: k_vol_forward_m), CB channels per launch.  COUNT (diagnostic,
 // dgs_volume_count_pairs): instead of the outputs, counts[0] += the pairs evaluated (candidates
-// inside their cut box) and counts[1] += the live ones (G > 0).
-template <int FN, int CB, bool COUNT = false>
+// inside their cut box) and counts[1] += the live ones (G > 0).  CF: VCoef for the operator, else
+// empty (as in every kernel below that has it).
+template <int FN, int CB, bool COUNT = false, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ buf, int P, int N, int C, int cbase,
                                                        const float *__restrict__ means,
                                                        const float *__restrict__ values,
                                                        const float *__restrict__ conics,
                                                        const float *__restrict__ samples, float *__restrict__ out,
-                                                       unsigned long long *__restrict__ counts = nullptr) {
+                                                       unsigned long long *__restrict__ counts = nullptr,
+                                                       CF... coef) {
     constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    const float *cf = coef_of(coef...);
     __shared__ VCand<CB> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -665,6 +709,10 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
                 if (!pair_eval(m, s, c, X, G, a)) return;
                 if constexpr (FN == kFnTrace) {  // no legacy bits to keep: the written-out sum (fwd_acc_c)
                     fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc);
+                    return;
+                }
+                if constexpr (FN == kFnOp) {  // (likewise)
+                    fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc, cf);
                     return;
                 }
                 terms<FN>(a, c, t);
@@ -720,18 +768,18 @@ __global__ __launch_bounds__(kBlock) void k_vol_hsum(int N, int C, const float *
 template <int FN, int CB>
 __device__ __forceinline__ void bwd_pair(const float *m, const float *c, const float *__restrict__ values, int g,
                                          int C, int cbase, int nch, const float *s, const float *hrow,
-                                         float *dm, float *dc, float *dv) {
+                                         float *dm, float *dc, float *dv, const float *cf = nullptr) {
     constexpr int KU = VTr<FN>::KU;
     float X[3], a[3], G, t[KU];
     if (!pair_eval(m, s, c, X, G, a)) return;
-    terms<FN>(a, c, t);
+    terms<FN>(a, c, t, cf);
     float hv[KU];
     if constexpr (CB == 1) {
         float p = 0.0f;
         for (int u = 0; u < KU; ++u) p += hrow[u] * t[u];
         dv[0] += G * p;
         float gg[3], e[6];
-        phi_grads<FN>(hrow, a, c, gg, e);
+        phi_grads<FN>(hrow, a, c, gg, e, cf);
         pair_grads(G, p, X, a, c, gg, e, dm, dc);
         return;
     } else {
@@ -749,7 +797,7 @@ __device__ __forceinline__ void bwd_pair(const float *m, const float *c, const f
     float phi = 0.0f;
     for (int u = 0; u < KU; ++u) phi += hv[u] * t[u];
     float gg[3], e[6];
-    phi_grads<FN>(hv, a, c, gg, e);
+    phi_grads<FN>(hv, a, c, gg, e, cf);
     pair_grads(G, phi, X, a, c, gg, e, dm, dc);
 }
 
@@ -758,6 +806,7 @@ __device__ __forceinline__ void bwd_pair(const float *m, const float *c, const f
 // the multiplicity of its index set, at staging), phi = sum_u h_u t_u and its partials are
 //   laplacian: phi = a.(H a) - H:c,          g = 2 H a,          e = -H (packed, off-diagonals x2)
 //   trace    : phi = H (a.a - tr c),         g = 2 H a,          e = -H on the diagonal (H a scalar)
+//   operator : phi = H t (op_t),             g = H (b + 2 W a),  e = -H m_u w_u          (H a scalar)
 //   third    : E_pq = H_pqk a_k, M = E a,     w_k = c_ij H_ijk,
 //              phi = 3 w.a - M.a,            g = 3 (w - M),      e = 3 E (off-diagonals x2)
 // and the pair only adds moments: G phi, G g, G phi X, G phi X X^T, G (g X^T + X g^T), G e.  The
@@ -779,7 +828,7 @@ __host__ __device__ constexpr float vol_inv_mult(int u) {
 // Entries a function does not have (g of the gaussian, e below the laplacian) are left as given.
 template <int FN>
 __device__ __forceinline__ void phi_ge_t(const float *H, const float *a, const float *c2, float &phi, float *g,
-                                         float *e) {
+                                         float *e, const float *cf = nullptr) {
     if constexpr (FN == 0) {
         phi = H[0];
     } else if constexpr (FN == 1) {
@@ -800,6 +849,9 @@ __device__ __forceinline__ void phi_ge_t(const float *H, const float *a, const f
         const float h2 = 2.0f * H[0];
         g[0] = h2 * a[0]; g[1] = h2 * a[1]; g[2] = h2 * a[2];
         e[0] = -H[0]; e[3] = -H[0]; e[5] = -H[0];
+    } else if constexpr (FN == kFnOp) {
+        phi = H[0] * op_t(a, c2, cf, 0.5f);
+        op_ge(H[0], a, cf, g, e);
     } else {
         // H000 H001 H002 H011 H012 H022 H111 H112 H122 H222 = H[0..9]
         const float E00 = H[0] * a[0] + H[1] * a[1] + H[2] * a[2];
@@ -891,15 +943,17 @@ __device__ __forceinline__ void bwd_store(int g, int C, int cbase, int nch, cons
 // and written once (no atomics).
 constexpr int kVolBwdBlocks = 8192;
 
-template <int FN, int CB>
+template <int FN, int CB, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__ buf, int P, int N, int C, int cbase,
                                                         const float *__restrict__ means,
                                                         const float *__restrict__ values,
                                                         const float *__restrict__ conics,
                                                         const float *__restrict__ samples,
                                                         const float *__restrict__ hs, float *__restrict__ dmeans,
-                                                        float *__restrict__ dvalues, float *__restrict__ dconics) {
+                                                        float *__restrict__ dvalues, float *__restrict__ dconics,
+                                                        CF... coef) {
     constexpr int KU = VTr<FN>::KU;
+    const float *cf = coef_of(coef...);
     __shared__ float4 scand[kWave];
     __shared__ float shrow[kWave][CB == 1 ? KU : 1];  // C == 1: the candidates' h rows
     const Hdr h = hdr_of(buf);
@@ -1003,7 +1057,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
                                                 else
                                                     bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sv,
                                                                      hs + (int64_t)__float_as_int(sp.w) * KU * C, dm,
-                                                                     dc, dv);
+                                                                     dc, dv, cf);
                                             }
                                         }
                                 }
@@ -1016,7 +1070,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
 }
 
 // Big Gaussians: one block each, threads striding over every sample, block sums.
-template <int FN, int CB>
+template <int FN, int CB, class... CF>
 __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restrict__ buf, int P, int N, int C,
                                                              int cbase, const float *__restrict__ means,
                                                              const float *__restrict__ values,
@@ -1025,8 +1079,9 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
                                                              const float *__restrict__ hs,
                                                              float *__restrict__ dmeans,
                                                              float *__restrict__ dvalues,
-                                                             float *__restrict__ dconics) {
+                                                             float *__restrict__ dconics, CF... coef) {
     constexpr int NV = 9 + CB;
+    const float *cf = coef_of(coef...);
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward writes the NaN)
@@ -1043,7 +1098,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
         for (int sid = threadIdx.x; sid < N; sid += kBlock) {
             const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
             bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sp,
-                             hs + (int64_t)sid * VTr<FN>::KU * C, v, v + 3, v + 9);
+                             hs + (int64_t)sid * VTr<FN>::KU * C, v, v + 3, v + 9, cf);
         }
         for (int k = 0; k < NV; ++k)
             for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
@@ -1078,10 +1133,11 @@ struct VOuts {
 // gaussian and fma(round(v G), t_u, acc) for the others; among the big Gaussians (BIG) the
 // product round(round(v G) t_u) is rounded on its own and then added.
 template <int FN, bool BIG>
-__device__ __forceinline__ void fwd_acc(float v, float G, const float *a, const float *c, float *acc) {
+__device__ __forceinline__ void fwd_acc(float v, float G, const float *a, const float *c, float *acc,
+                                        const float *cf = nullptr) {
     constexpr int KU = VTr<FN>::KU;
     float t[KU];
-    terms<FN>(a, c, t);
+    terms<FN>(a, c, t, cf);
     if constexpr (BIG) {
         const float vG = rmul(v, G);
         for (int u = 0; u < KU; ++u) acc[u] = radd(acc[u], rmul(vG, t[u]));
@@ -1103,15 +1159,18 @@ __device__ __forceinline__ void fwd_nan(float *__restrict__ out, int64_t sid) {
     for (int f = 0; f < K; ++f) out[sid * K + f] = NAN;
 }
 
-template <int MASK>
+template <int MASK, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict__ buf, int P, int N,
                                                          const float *__restrict__ means,
                                                          const float *__restrict__ values,
                                                          const float *__restrict__ conics,
-                                                         const float *__restrict__ samples, VOuts outs) {
+                                                         const float *__restrict__ samples, VOuts outs,
+                                                         CF... coef) {
     constexpr int SKU = mask_ku(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
     constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
+    constexpr int O5 = mask_off(MASK, kFnOp), S5 = fn_slot(kFnOp);
+    const float *cf = coef_of(coef...);
     __shared__ VCand<1> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1122,6 +1181,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
             if constexpr ((MASK & 4) != 0) fwd_nan<2>(outs.p[2], j);
             if constexpr ((MASK & 8) != 0) fwd_nan<3>(outs.p[3], j);
             if constexpr ((MASK & 16) != 0) fwd_nan<kFnTrace>(outs.p[S4], j);
+            if constexpr ((MASK & 32) != 0) fwd_nan<kFnOp>(outs.p[S5], j);
         }
         return;
     }
@@ -1146,6 +1206,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 4) != 0) fwd_acc<2, BIG>(v, G, a, c, acc + O2);
                 if constexpr ((MASK & 8) != 0) fwd_acc<3, BIG>(v, G, a, c, acc + O3);
                 if constexpr ((MASK & 16) != 0) fwd_acc<kFnTrace, BIG>(v, G, a, c, acc + O4);
+                if constexpr ((MASK & 32) != 0) fwd_acc<kFnOp, BIG>(v, G, a, c, acc + O5, cf);
             };
             walk_candidates<1>(
                 h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
@@ -1163,6 +1224,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 4) != 0) fwd_store<2>(outs.p[2], sid, acc + O2);
                 if constexpr ((MASK & 8) != 0) fwd_store<3>(outs.p[3], sid, acc + O3);
                 if constexpr ((MASK & 16) != 0) fwd_store<kFnTrace>(outs.p[S4], sid, acc + O4);
+                if constexpr ((MASK & 32) != 0) fwd_store<kFnOp>(outs.p[S5], sid, acc + O5);
             }
         }
     }
@@ -1190,9 +1252,9 @@ __device__ __forceinline__ void stage_h(float *row, const float *__restrict__ hr
 // phi, g and e of function FN added to the pair's sums
 template <int FN>
 __device__ __forceinline__ void phi_ge_add(const float *H, const float *a, const float *c2, float &phi, float *g,
-                                           float *e) {
+                                           float *e, const float *cf = nullptr) {
     float p, gf[3] = {0.0f, 0.0f, 0.0f}, ef[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    phi_ge_t<FN>(H, a, c2, p, gf, ef);
+    phi_ge_t<FN>(H, a, c2, p, gf, ef, cf);
     phi += p;
     if constexpr (FN >= 1)
         for (int d = 0; d < 3; ++d) g[d] += gf[d];
@@ -1200,17 +1262,20 @@ __device__ __forceinline__ void phi_ge_add(const float *H, const float *a, const
         for (int q = 0; q < 6; ++q) e[q] += ef[q];
 }
 
-template <int MASK>
+template <int MASK, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict__ buf, int P, int N,
                                                           const float *__restrict__ means,
                                                           const float *__restrict__ values,
                                                           const float *__restrict__ conics,
                                                           const float *__restrict__ samples,
                                                           const float *__restrict__ hs, float *__restrict__ dmeans,
-                                                          float *__restrict__ dvalues, float *__restrict__ dconics) {
+                                                          float *__restrict__ dvalues, float *__restrict__ dconics,
+                                                          CF... coef) {
     constexpr int SKU = mask_ku(MASK), TOP = mask_top(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
     constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
+    constexpr int O5 = mask_off(MASK, kFnOp);
+    const float *cf = coef_of(coef...);
     __shared__ float4 scand[kWave];
     __shared__ float shrow[kWave][SKU];  // the candidates' H rows, function after function
     const Hdr &h = hdr_of(buf);  // (in place, as k_vol_forward_m)
@@ -1295,6 +1360,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                         if constexpr ((MASK & 4) != 0) stage_h<2>(&shrow[lane][O2], hrow + O2);
                                         if constexpr ((MASK & 8) != 0) stage_h<3>(&shrow[lane][O3], hrow + O3);
                                         if constexpr ((MASK & 16) != 0) stage_h<kFnTrace>(&shrow[lane][O4], hrow + O4);
+                                        if constexpr ((MASK & 32) != 0) stage_h<kFnOp>(&shrow[lane][O5], hrow + O5);
                                     }
                                     __syncthreads();
                                     const int cnt = min(kWave, e - q0);
@@ -1318,6 +1384,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                             if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, gg, ee);
                                             if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, gg, ee);
                                             if constexpr ((MASK & 16) != 0) phi_ge_add<kFnTrace>(H + O4, a, c2, phi, gg, ee);
+                                            if constexpr ((MASK & 32) != 0) phi_ge_add<kFnOp>(H + O5, a, c2, phi, gg, ee, cf);
                                             vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
                                         }
                                 }
@@ -1332,7 +1399,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
 
 // Big Gaussians of the fused backward: the per-function pair terms into the same sums, rows
 // written once.
-template <int MASK>
+template <int MASK, class... CF>
 __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__restrict__ buf, int P, int N,
                                                                const float *__restrict__ means,
                                                                const float *__restrict__ values,
@@ -1341,8 +1408,9 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
                                                                const float *__restrict__ hs,
                                                                float *__restrict__ dmeans,
                                                                float *__restrict__ dvalues,
-                                                               float *__restrict__ dconics) {
+                                                               float *__restrict__ dconics, CF... coef) {
     constexpr int NV = 10, SKU = mask_ku(MASK);
+    const float *cf = coef_of(coef...);
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_m writes the NaN)
@@ -1369,6 +1437,8 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
                 bwd_pair<3, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
             if constexpr ((MASK & 16) != 0)
                 bwd_pair<kFnTrace, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnTrace), v, v + 3, v + 9);
+            if constexpr ((MASK & 32) != 0)
+                bwd_pair<kFnOp, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnOp), v, v + 3, v + 9, cf);
         }
         for (int k = 0; k < NV; ++k)
             for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
@@ -1417,16 +1487,18 @@ struct VDLs {
 };
 
 // C = 1, every mask
-template <int MASK>
+template <int MASK, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ buf, int P, int N,
                                                        const float *__restrict__ means,
                                                        const float *__restrict__ values,
                                                        const float *__restrict__ conics,
                                                        const float *__restrict__ samples, VDLs dLs,
-                                                       float *__restrict__ dsamples) {
+                                                       float *__restrict__ dsamples, CF... coef) {
     constexpr int SKU = mask_ku(MASK);
     constexpr int O0 = mask_off(MASK, 0), O1 = mask_off(MASK, 1), O2 = mask_off(MASK, 2), O3 = mask_off(MASK, 3);
     constexpr int O4 = mask_off(MASK, kFnTrace), S4 = fn_slot(kFnTrace);
+    constexpr int O5 = mask_off(MASK, kFnOp), S5 = fn_slot(kFnOp);
+    const float *cf = coef_of(coef...);
     __shared__ VCand<1> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1452,6 +1524,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 if constexpr ((MASK & 4) != 0) sg_load_h<2>(dLs.p[2], sid, H + O2);
                 if constexpr ((MASK & 8) != 0) sg_load_h<3>(dLs.p[3], sid, H + O3);
                 if constexpr ((MASK & 16) != 0) sg_load_h<kFnTrace>(dLs.p[S4], sid, H + O4);
+                if constexpr ((MASK & 32) != 0) sg_load_h<kFnOp>(dLs.p[S5], sid, H + O5);
             }
             float ds[3] = {0.0f, 0.0f, 0.0f};
             auto eval = [&](const float *m, const float *c, float v) {
@@ -1464,6 +1537,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 if constexpr ((MASK & 4) != 0) phi_ge_add<2>(H + O2, a, c2, phi, g, e);
                 if constexpr ((MASK & 8) != 0) phi_ge_add<3>(H + O3, a, c2, phi, g, e);
                 if constexpr ((MASK & 16) != 0) phi_ge_add<kFnTrace>(H + O4, a, c2, phi, g, e);
+                if constexpr ((MASK & 32) != 0) phi_ge_add<kFnOp>(H + O5, a, c2, phi, g, e, cf);
                 sg_add(v * G, phi, a, c, g, ds);
             };
             walk_candidates<1>(
@@ -1485,14 +1559,16 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
 
 // C > 1, one function, CB channels per launch: hv_u = sum_ch v_ch h_u,ch over the block's channels
 // per pair; the launches after the first (cbase > 0) add onto the owning lane's stored row.
-template <int FN, int CB>
+template <int FN, int CB, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ buf, int P, int N, int C, int cbase,
                                                      const float *__restrict__ means,
                                                      const float *__restrict__ values,
                                                      const float *__restrict__ conics,
                                                      const float *__restrict__ samples,
-                                                     const float *__restrict__ dL, float *__restrict__ dsamples) {
+                                                     const float *__restrict__ dL, float *__restrict__ dsamples,
+                                                     CF... coef) {
     constexpr int KU = VTr<FN>::KU, K = VTr<FN>::K;
+    const float *cf = coef_of(coef...);
     __shared__ VCand<CB> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1537,7 +1613,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ bu
                 }
                 const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
                 float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
-                phi_ge_t<FN>(hv, a, c2, phi, g, e);
+                phi_ge_t<FN>(hv, a, c2, phi, g, e, cf);
                 sg_add(G, phi, a, c, g, ds);
             };
             walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
@@ -1571,6 +1647,7 @@ __host__ __device__ __forceinline__ void for_mask(F f) {  // f(integral_constant
     if constexpr ((MASK & 4) != 0) f(std::integral_constant<int, 2>{});
     if constexpr ((MASK & 8) != 0) f(std::integral_constant<int, 3>{});
     if constexpr ((MASK & 16) != 0) f(std::integral_constant<int, kFnTrace>{});
+    if constexpr ((MASK & 32) != 0) f(std::integral_constant<int, kFnOp>{});
 }
 
 // acc[u][ch] += v_ch G t_u for function FN with every rounding written out, so that an output does
@@ -1579,10 +1656,10 @@ __host__ __device__ __forceinline__ void for_mask(F f) {  // f(integral_constant
 // alike.  These are the roundings the compiler gives k_vol_forward<FN, 4>.
 template <int FN, int CB>
 __device__ __forceinline__ void fwd_acc_c(int nch, const float *vr, float G, const float *a, const float *c,
-                                          float (*acc)[CB]) {
+                                          float (*acc)[CB], const float *cf) {
     constexpr int KU = VTr<FN>::KU;
     float t[KU];
-    terms<FN>(a, c, t);
+    terms<FN>(a, c, t, cf);
 #pragma unroll
     for (int ch = 0; ch < CB; ++ch) {
         if (ch >= nch) continue;
@@ -1596,13 +1673,15 @@ __device__ __forceinline__ void fwd_acc_c(int nch, const float *vr, float G, con
     }
 }
 
-template <int MASK, int CB>
+template <int MASK, int CB, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict__ buf, int P, int N, int C,
                                                           const float *__restrict__ means,
                                                           const float *__restrict__ values,
                                                           const float *__restrict__ conics,
-                                                          const float *__restrict__ samples, VOuts outs) {
+                                                          const float *__restrict__ samples, VOuts outs,
+                                                          CF... coef) {
     constexpr int SKU = mask_ku(MASK);
+    const float *cf = coef_of(coef...);
     __shared__ VCand<CB> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1637,7 +1716,7 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict
                 if (!pair_eval(m, s, c, X, G, a)) return;
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value;
-                    fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc + mask_off(MASK, FN));
+                    fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc + mask_off(MASK, FN), cf);
                 });
             };
             walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
@@ -1745,15 +1824,17 @@ __device__ __forceinline__ void walk_samples(const Hdr &h, const int32_t *__rest
 // column per channel, the columns >= C selected to 0).  Per kept pair hv_u = sum_ch v_ch H_ch,u, then
 // phi, g, e of hv over the mask's functions and one vol_mom_add; dv[ch] += G phi(H_ch).  v is inside
 // hv, so the rows are stored with scale 1.  No atomics, a fixed order of additions.
-template <int MASK, int CB>
+template <int MASK, int CB, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restrict__ buf, int P, int N, int C,
                                                            const float *__restrict__ means,
                                                            const float *__restrict__ values,
                                                            const float *__restrict__ conics,
                                                            const float *__restrict__ samples,
                                                            const float *__restrict__ hs, float *__restrict__ dmeans,
-                                                           float *__restrict__ dvalues, float *__restrict__ dconics) {
+                                                           float *__restrict__ dvalues, float *__restrict__ dconics,
+                                                           CF... coef) {
     constexpr int SKU = mask_ku(MASK), TOP = mask_top(MASK);
+    const float *cf = coef_of(coef...);
     __shared__ float4 scand[kWave];
     __shared__ float shrow[kWave][CB][SKU];  // the candidates' H, channel after channel
     const Hdr &h = hdr_of(buf);
@@ -1811,7 +1892,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restric
                     float p = 0.0f, gd[3] = {0.0f, 0.0f, 0.0f}, ed[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (gd, ed unused)
                     for_mask<MASK>([&](auto fc) {
                         constexpr int FN = decltype(fc)::value;
-                        phi_ge_add<FN>(H + mask_off(MASK, FN), a, c2, p, gd, ed);
+                        phi_ge_add<FN>(H + mask_off(MASK, FN), a, c2, p, gd, ed, cf);
                     });
                     dv[ch] += G * p;
 #pragma unroll
@@ -1820,7 +1901,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restric
                 float phi = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f}, ee[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value;
-                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, gg, ee);
+                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, gg, ee, cf);
                 });
                 vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
             };
@@ -1834,7 +1915,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restric
 
 // Big Gaussians of the fused backward at C = 2..4: the per-function pair terms (bwd_pair<FN, CB> on
 // function FN's slice of the row) into the same block sums, rows written once.
-template <int MASK, int CB>
+template <int MASK, int CB, class... CF>
 __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__restrict__ buf, int P, int N, int C,
                                                                 const float *__restrict__ means,
                                                                 const float *__restrict__ values,
@@ -1843,8 +1924,9 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__re
                                                                 const float *__restrict__ hs,
                                                                 float *__restrict__ dmeans,
                                                                 float *__restrict__ dvalues,
-                                                                float *__restrict__ dconics) {
+                                                                float *__restrict__ dconics, CF... coef) {
     constexpr int NV = 9 + CB, SKU = mask_ku(MASK);
+    const float *cf = coef_of(coef...);
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_mc writes the NaN)
@@ -1863,7 +1945,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__re
             const float *hrow = hs + (int64_t)sid * SKU * C;
             for_mask<MASK>([&](auto fc) {
                 constexpr int FN = decltype(fc)::value;
-                bwd_pair<FN, CB>(m, c, values, g, C, 0, nch, sp, hrow + mask_off(MASK, FN) * C, v, v + 3, v + 9);
+                bwd_pair<FN, CB>(m, c, values, g, C, 0, nch, sp, hrow + mask_off(MASK, FN) * C, v, v + 3, v + 9, cf);
             });
         }
         for (int k = 0; k < NV; ++k)
@@ -1886,14 +1968,15 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__re
 // The sample gradient of several functions at C = 2..4: k_vol_sgrad's lane (the tensor H per channel
 // in registers, hv per pair) with phi and g summed over the mask's functions, as k_vol_sgrad_m does.
 // Three sums per lane, one store, no cross-lane sums.
-template <int MASK, int CB>
+template <int MASK, int CB, class... CF>
 __global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__ buf, int P, int N, int C,
                                                         const float *__restrict__ means,
                                                         const float *__restrict__ values,
                                                         const float *__restrict__ conics,
                                                         const float *__restrict__ samples, VDLs dLs,
-                                                        float *__restrict__ dsamples) {
+                                                        float *__restrict__ dsamples, CF... coef) {
     constexpr int SKU = mask_ku(MASK);
+    const float *cf = coef_of(coef...);
     __shared__ VCand<CB> cand[kWave];
     const Hdr &h = hdr_of(buf);
     const int lane = threadIdx.x;
@@ -1946,7 +2029,7 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__
                 float phi = 0.0f, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value;
-                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, g, e);
+                    phi_ge_add<FN>(hv + mask_off(MASK, FN), a, c2, phi, g, e, cf);
                 });
                 sg_add(G, phi, a, c, g, ds);
             };
@@ -1974,21 +2057,24 @@ struct VArgs {  // what every launch takes
     hipStream_t s;
 };
 
-// The kernels' pointer structs from the caller's per-code arrays: four entries, or five (read only
-// when the mask holds the trace, whose pointer goes into its slot).
+// The kernels' pointer structs from the caller's per-code arrays: four entries, or five / six (read
+// only when the mask holds the trace / the operator, whose pointer goes into its slot).  The
+// launches below take the operator's VCoef as a trailing argument and hand it on; none otherwise.
 template <int MASK, class S, class T>
 static S slots_of(T *const *ptrs) {
     S o;
     for (int f = 0; f < 4; ++f) o.p[f] = (MASK >> f) & 1 ? ptrs[f] : nullptr;
     if constexpr ((MASK & 16) != 0) o.p[fn_slot(kFnTrace)] = ptrs[kFnTrace];
+    if constexpr ((MASK & 32) != 0) o.p[fn_slot(kFnOp)] = ptrs[kFnOp];
     return o;
 }
 
 // C = 1: every function mask
-template <int MASK>
-static void launch_fwd_m(const VArgs &a, float *const *outs) {
+template <int MASK, class... CF>
+static void launch_fwd_m(const VArgs &a, float *const *outs, const CF &...cf) {
     const VOuts o = slots_of<MASK, VOuts>(outs);
-    k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, o);
+    k_vol_forward_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, o,
+                                                            cf...);
 }
 template <int FN>
 static void launch_hsum_cat(int mask, int N, const float *const *dLs, float *hs, hipStream_t s) {
@@ -1996,61 +2082,65 @@ static void launch_hsum_cat(int mask, int N, const float *const *dLs, float *hs,
     k_vol_hsum_cat<FN><<<(unsigned)((N + kBlock - 1) / kBlock), kBlock, 0, s>>>(N, dLs[FN], hs, mask_ku(mask),
                                                                                  mask_off(mask, FN));
 }
-template <int MASK>
-static void launch_bwd_m(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc) {
+template <int MASK, class... CF>
+static void launch_bwd_m(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc,
+                         const CF &...cf) {
     launch_hsum_cat<0>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<1>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<2>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<3>(MASK, a.N, dLs, hs, a.s);
     launch_hsum_cat<kFnTrace>(MASK, a.N, dLs, hs, a.s);
+    launch_hsum_cat<kFnOp>(MASK, a.N, dLs, hs, a.s);
     k_vol_backward_m<MASK><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples,
-                                                             hs, dm, dv, dc);
+                                                             hs, dm, dv, dc, cf...);
     k_vol_backward_big_m<MASK><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, hs,
-                                                        dm, dv, dc);
+                                                        dm, dv, dc, cf...);
 }
 
 // one function, CB = 1 (the backward at C = 1), 4 (C <= 4) or 8 channels per launch
-template <int FN, int CB>
-static void launch_fwd(const VArgs &a, float *out) {
+template <int FN, int CB, class... CF>
+static void launch_fwd(const VArgs &a, float *out, const CF &...cf) {
     for (int cb = 0; cb < a.C; cb += CB)
         k_vol_forward<FN, CB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
-                                                                a.samples, out);
+                                                                a.samples, out, (unsigned long long *)nullptr, cf...);
 }
-template <int FN, int CB>
-static void launch_bwd(const VArgs &a, const float *dL, float *hs, float *dm, float *dv, float *dc) {
+template <int FN, int CB, class... CF>
+static void launch_bwd(const VArgs &a, const float *dL, float *hs, float *dm, float *dv, float *dc, const CF &...cf) {
     const int64_t nh = (int64_t)a.N * a.C;
     k_vol_hsum<FN><<<(unsigned)((nh + kBlock - 1) / kBlock), kBlock, 0, a.s>>>(a.N, a.C, dL, hs);
     for (int cb = 0; cb < a.C; cb += CB) {
         k_vol_backward<FN, CB><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values,
-                                                                 a.conics, a.samples, hs, dm, dv, dc);
+                                                                 a.conics, a.samples, hs, dm, dv, dc, cf...);
         k_vol_backward_big<FN, CB><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
-                                                            a.samples, hs, dm, dv, dc);
+                                                            a.samples, hs, dm, dv, dc, cf...);
     }
 }
 
 // sample gradients: every mask at C = 1; one function, 4 (C <= 4) or 8 channels per launch
-template <int MASK>
-static void launch_sgrad_m(const VArgs &a, const float *const *dLs, float *ds) {
+template <int MASK, class... CF>
+static void launch_sgrad_m(const VArgs &a, const float *const *dLs, float *ds, const CF &...cf) {
     const VDLs d = slots_of<MASK, VDLs>(dLs);
-    k_vol_sgrad_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, d, ds);
+    k_vol_sgrad_m<MASK><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.means, a.values, a.conics, a.samples, d, ds,
+                                                          cf...);
 }
-template <int FN, int CB>
-static void launch_sgrad(const VArgs &a, const float *dL, float *ds) {
+template <int FN, int CB, class... CF>
+static void launch_sgrad(const VArgs &a, const float *dL, float *ds, const CF &...cf) {
     for (int cb = 0; cb < a.C; cb += CB)
         k_vol_sgrad<FN, CB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, cb, a.means, a.values, a.conics,
-                                                              a.samples, dL, ds);
+                                                              a.samples, dL, ds, cf...);
 }
 
 // C = 2..4: two or more functions, the one channel block of 4
 constexpr int kVolFusedCB = DGS_VOLUME_FUSED_MAX_C;
-template <int MASK>
-static void launch_fwd_mc(const VArgs &a, float *const *outs) {
+template <int MASK, class... CF>
+static void launch_fwd_mc(const VArgs &a, float *const *outs, const CF &...cf) {
     const VOuts o = slots_of<MASK, VOuts>(outs);
     k_vol_forward_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
-                                                                          a.conics, a.samples, o);
+                                                                          a.conics, a.samples, o, cf...);
 }
-template <int MASK>
-static void launch_bwd_mc(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc) {
+template <int MASK, class... CF>
+static void launch_bwd_mc(const VArgs &a, const float *const *dLs, float *hs, float *dm, float *dv, float *dc,
+                          const CF &...cf) {
     const int64_t nh = (int64_t)a.N * a.C;
     for_mask<MASK>([&](auto fc) {
         constexpr int FN = decltype(fc)::value;
@@ -2058,15 +2148,16 @@ static void launch_bwd_mc(const VArgs &a, const float *const *dLs, float *hs, fl
             a.N, a.C, dLs[FN], hs, mask_ku(MASK) * a.C, mask_off(MASK, FN) * a.C);
     });
     k_vol_backward_mc<MASK, kVolFusedCB><<<kVolBwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
-                                                                           a.conics, a.samples, hs, dm, dv, dc);
+                                                                           a.conics, a.samples, hs, dm, dv, dc,
+                                                                           cf...);
     k_vol_backward_big_mc<MASK, kVolFusedCB><<<256, kBlock, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
-                                                                      a.conics, a.samples, hs, dm, dv, dc);
+                                                                      a.conics, a.samples, hs, dm, dv, dc, cf...);
 }
-template <int MASK>
-static void launch_sgrad_mc(const VArgs &a, const float *const *dLs, float *ds) {
+template <int MASK, class... CF>
+static void launch_sgrad_mc(const VArgs &a, const float *const *dLs, float *ds, const CF &...cf) {
     const VDLs d = slots_of<MASK, VDLs>(dLs);
     k_vol_sgrad_mc<MASK, kVolFusedCB><<<kVolFwdBlocks, kWave, 0, a.s>>>(a.buf, a.P, a.N, a.C, a.means, a.values,
-                                                                        a.conics, a.samples, d, ds);
+                                                                        a.conics, a.samples, d, ds, cf...);
 }
 
 // the masks of the forward kernels (all 15) and of the fused backward (two or more functions)
@@ -2081,6 +2172,9 @@ static int fn_cb_case(int mask, int C) { return mask_top(mask) * 3 + (C <= 1 ? 0
 // the masks with the trace (dgs_volume_*_ops): alone, and with a non-empty subset of {0, 1, 3}
 #define DGS_VOL_MASKS_TRACE_FUSED(X) X(17) X(18) X(19) X(24) X(25) X(26) X(27)
 #define DGS_VOL_MASKS_TRACE(X) X(16) DGS_VOL_MASKS_TRACE_FUSED(X)
+// the masks with the operator (dgs_volume_*_linop): alone, and with a non-empty subset of {0, 1}
+#define DGS_VOL_MASKS_OP_FUSED(X) X(33) X(34) X(35)
+#define DGS_VOL_MASKS_OP(X) X(32) DGS_VOL_MASKS_OP_FUSED(X)
 
 }  // namespace vol
 }  // namespace dgs
@@ -2637,6 +2731,161 @@ extern "C" int dgs_volume_backward_samples_ops(int mask, int P, int N, int C, co
         switch (mask) {
 #define X(M) case M: launch_sgrad_mc<M>(a, dL_douts, dL_dsamples); break;
             DGS_VOL_MASKS_TRACE_FUSED(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+// ---- the *_linop entries: the *_ops entries plus function 5, the linear operator (bit 5), whose ten
+// coefficients come as a host pointer and go to the kernels by value.  A mask below 32 is the *_ops
+// entry itself; the operator alone runs at any C (C = 1: the mask kernels, C > 1: the per-function
+// kernels in channel blocks of 4 / 8); the operator with the gaussian and / or the derivative takes
+// the mask kernels at C = 1 and the _mc kernels at 2 <= C <= DGS_VOLUME_FUSED_MAX_C.
+static bool linop_mask_ok(int mask) { return mask >= 32 ? mask <= 35 : ops_mask_ok(mask); }
+static int vol_check_linop(int mask, const float *coef, int P, int N, int C, const void *binning, size_t bytes,
+                           VCoef &cf) {
+    if (!linop_mask_ok(mask))
+        return fail(DGS_ERR_ARG, "dgs_volume_*_linop: mask must be 1..63, the operator (32) only with the gaussian (1) "
+                                 "and the derivative (2)");
+    if (!coef) return fail(DGS_ERR_ARG, "dgs_volume_*_linop: coef (ten floats) required with the operator");
+    for (int i = 0; i < 10; ++i)
+        if (!std::isfinite(coef[i])) return fail(DGS_ERR_ARG, "dgs_volume_*_linop: coef must be finite");
+    if (P < 0 || N < 0 || C < 1) return fail(DGS_ERR_ARG, "dgs_volume: bad sizes");
+    if (mask != 32 && C > DGS_VOLUME_FUSED_MAX_C)
+        return fail(DGS_ERR_ARG, "dgs_volume_*_linop: several functions need C <= 4 (DGS_VOLUME_FUSED_MAX_C); "
+                                 "call them per function and add");
+    if (!binning || bytes < kHdrBytes) return fail(DGS_ERR_BUFFER, "dgs_volume: binning buffer missing or too small");
+    for (int i = 0; i < 10; ++i) cf.k[i] = (i == 5 || i == 6 || i == 8 ? 2.0f : 1.0f) * coef[i];  // m_u w_u
+    return DGS_OK;
+}
+
+extern "C" size_t dgs_volume_workspace_size_linop(int mask, int P, int N, int C, int backward) {
+    if (!linop_mask_ok(mask)) return 0;
+    if (mask < 32) return dgs_volume_workspace_size_ops(mask, P, N, C, backward);
+    if (!backward || N <= 0 || C <= 0 || (mask != 32 && C > DGS_VOLUME_FUSED_MAX_C)) return 0;
+    return (size_t)N * mask_ku(mask) * C * 4;  // hs[N][unique components of the mask][C]
+}
+
+extern "C" int dgs_volume_forward_linop(int mask, const float *coef, int P, int N, int C, const float *means,
+                                        const float *values, const float *conics, const float *samples,
+                                        const void *binning, size_t binning_bytes, float *const *outs,
+                                        dgs_stream_t stream, int debug) {
+    if (linop_mask_ok(mask) && mask < 32)
+        return dgs_volume_forward_ops(mask, P, N, C, means, values, conics, samples, binning, binning_bytes, outs,
+                                      stream, debug);
+    VCoef cf;
+    if (int rc = vol_check_linop(mask, coef, P, N, C, binning, binning_bytes, cf)) return rc;
+    if (!outs) return fail(DGS_ERR_ARG, "dgs_volume_forward_linop: outs required");
+    if (N == 0) return DGS_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_fwd_m<M>(a, outs, cf); break;
+            DGS_VOL_MASKS_OP(X)
+#undef X
+        }
+    } else if (mask == 32) {
+        if (C <= 4) launch_fwd<kFnOp, 4>(a, outs[kFnOp], cf);
+        else launch_fwd<kFnOp, 8>(a, outs[kFnOp], cf);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_fwd_mc<M>(a, outs, cf); break;
+            DGS_VOL_MASKS_OP_FUSED(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_linop(int mask, const float *coef, int P, int N, int C, const float *means,
+                                         const float *values, const float *conics, const float *samples,
+                                         const float *const *dL_douts, const void *binning, size_t binning_bytes,
+                                         float *dL_dmeans, float *dL_dvalues, float *dL_dconics, void *workspace,
+                                         size_t workspace_bytes, dgs_stream_t stream, int debug) {
+    if (linop_mask_ok(mask) && mask < 32)
+        return dgs_volume_backward_ops(mask, P, N, C, means, values, conics, samples, dL_douts, binning, binning_bytes,
+                                       dL_dmeans, dL_dvalues, dL_dconics, workspace, workspace_bytes, stream, debug);
+    VCoef cf;
+    if (int rc = vol_check_linop(mask, coef, P, N, C, binning, binning_bytes, cf)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_linop: dL_douts required");
+    if (workspace_bytes < dgs_volume_workspace_size_linop(mask, P, N, C, 1) || (N > 0 && P > 0 && !workspace))
+        return fail(DGS_ERR_ARG, "dgs_volume_backward_linop: workspace missing or too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) return DGS_OK;
+    if (N == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dmeans, 0, (size_t)P * 12, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dvalues, 0, (size_t)P * C * 4, s));
+        DGS_TRY_HIP(hipMemsetAsync(dL_dconics, 0, (size_t)P * 24, s));
+        return DGS_OK;
+    }
+    for (int f = 0; f < 6; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_linop: a dL_dout of the mask is NULL");
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    float *hs = static_cast<float *>(workspace);
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_bwd_m<M>(a, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics, cf); break;
+            DGS_VOL_MASKS_OP(X)
+#undef X
+        }
+    } else if (mask == 32) {
+        if (C <= 4) launch_bwd<kFnOp, 4>(a, dL_douts[kFnOp], hs, dL_dmeans, dL_dvalues, dL_dconics, cf);
+        else launch_bwd<kFnOp, 8>(a, dL_douts[kFnOp], hs, dL_dmeans, dL_dvalues, dL_dconics, cf);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_bwd_mc<M>(a, dL_douts, hs, dL_dmeans, dL_dvalues, dL_dconics, cf); break;
+            DGS_VOL_MASKS_OP_FUSED(X)
+#undef X
+        }
+    }
+    DGS_LAUNCH_CHECK(s, debug);
+    return DGS_OK;
+}
+
+extern "C" int dgs_volume_backward_samples_linop(int mask, const float *coef, int P, int N, int C,
+                                                 const float *means, const float *values, const float *conics,
+                                                 const float *samples, const float *const *dL_douts,
+                                                 const void *binning, size_t binning_bytes, float *dL_dsamples,
+                                                 void *workspace, size_t workspace_bytes, dgs_stream_t stream,
+                                                 int debug) {
+    if (linop_mask_ok(mask) && mask < 32)
+        return dgs_volume_backward_samples_ops(mask, P, N, C, means, values, conics, samples, dL_douts, binning,
+                                               binning_bytes, dL_dsamples, workspace, workspace_bytes, stream, debug);
+    VCoef cf;
+    if (int rc = vol_check_linop(mask, coef, P, N, C, binning, binning_bytes, cf)) return rc;
+    if (!dL_douts) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_linop: dL_douts required");
+    if (N == 0) return DGS_OK;
+    if (!dL_dsamples) return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_linop: dL_dsamples required");
+    for (int f = 0; f < 6; ++f)
+        if (((mask >> f) & 1) && !dL_douts[f])
+            return fail(DGS_ERR_ARG, "dgs_volume_backward_samples_linop: a dL_dout of the mask is NULL");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P == 0) {
+        DGS_TRY_HIP(hipMemsetAsync(dL_dsamples, 0, (size_t)N * 12, s));
+        return DGS_OK;
+    }
+    if (int rc = vol_flag_reset_verify(P, N, means, conics, samples, binning, s)) return rc;
+    const VArgs a{static_cast<const char *>(binning), P, N, C, means, values, conics, samples, s};
+    if (C == 1) {
+        switch (mask) {
+#define X(M) case M: launch_sgrad_m<M>(a, dL_douts, dL_dsamples, cf); break;
+            DGS_VOL_MASKS_OP(X)
+#undef X
+        }
+    } else if (mask == 32) {
+        if (C <= 4) launch_sgrad<kFnOp, 4>(a, dL_douts[kFnOp], dL_dsamples, cf);
+        else launch_sgrad<kFnOp, 8>(a, dL_douts[kFnOp], dL_dsamples, cf);
+    } else {
+        switch (mask) {
+#define X(M) case M: launch_sgrad_mc<M>(a, dL_douts, dL_dsamples, cf); break;
+            DGS_VOL_MASKS_OP_FUSED(X)
 #undef X
         }
     }

@@ -10,6 +10,7 @@
 //   * opaque u8 buffers come back to Python and are handed back verbatim;
 //   * everything runs on torch's current HIP stream; `debug` synchronises and checks after
 //     every launch (auxiliary.h:33-40).
+#include <array>
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
@@ -1370,6 +1371,175 @@ Tensor VolumeSamplesBackwardOps(const std::vector<int64_t> &codes, const Tensor 
     return ds;
 }
 
+// ---- the six functions of a D = 3 field (dgs_volume_*_linop): the codes of the bindings above plus
+// 5, the constant-coefficient linear operator ([N, C]), whose ten coefficients `coef` are host
+// numbers of this call.  One C call when the entry takes the mask: the operator alone, or with the
+// gaussian and / or the derivative at C <= DGS_VOLUME_FUSED_MAX_C.  Otherwise: with more channels
+// every function on its own; with the laplacian, the third derivative or the trace, the operator as
+// its own call beside the groups of the rest (ops_groups).  Gradients are added.
+static std::vector<std::vector<size_t>> linop_groups(const std::vector<int64_t> &codes, int64_t C) {
+    int mask = 0;
+    for (int64_t f : codes) {
+        TORCH_CHECK(f >= 0 && f <= DGS_VOLUME_FN_OPERATOR, "volume: function codes are 0..5");
+        TORCH_CHECK(!(mask & (1 << f)), "each sampling function may appear once");
+        mask |= 1 << f;
+    }
+    TORCH_CHECK(mask != 0, "no sampling function given");
+    std::vector<std::vector<size_t>> groups;
+    if (codes.size() > 1 && C > DGS_VOLUME_FUSED_MAX_C) {
+        for (size_t i = 0; i < codes.size(); ++i) groups.push_back({i});
+    } else if ((mask & 32) && (mask & (4 | 8 | 16))) {
+        std::vector<int64_t> rest;
+        std::vector<size_t> pos;
+        for (size_t i = 0; i < codes.size(); ++i)
+            if (codes[i] != DGS_VOLUME_FN_OPERATOR) {
+                rest.push_back(codes[i]);
+                pos.push_back(i);
+            }
+        for (const auto &g : ops_groups(rest, C)) {
+            groups.emplace_back();
+            for (size_t i : g) groups.back().push_back(pos[i]);
+        }
+        for (size_t i = 0; i < codes.size(); ++i)
+            if (codes[i] == DGS_VOLUME_FN_OPERATOR) groups.push_back({i});
+    } else {
+        groups.emplace_back();
+        for (size_t i = 0; i < codes.size(); ++i) groups.back().push_back(i);
+    }
+    return groups;
+}
+static int64_t linop_k(int64_t code) { return code == DGS_VOLUME_FN_OPERATOR ? 1 : ops_k(code); }
+static std::array<float, 10> linop_coef(const std::vector<double> &coef) {
+    TORCH_CHECK(coef.size() == 10, "volume: coef is ten numbers [c0, b0, b1, b2, w00, w01, w02, w11, w12, w22]");
+    std::array<float, 10> c;
+    for (int i = 0; i < 10; ++i) c[i] = (float)coef[i];
+    return c;
+}
+
+std::vector<Tensor> VolumeForwardLinop(const std::vector<int64_t> &codes, const std::vector<double> &coef_in,
+                                       const Tensor &means_in, const Tensor &values_in, const Tensor &conics_in,
+                                       const Tensor &samples_in, const Tensor &binning_in, const bool debug) {
+    const auto coef = linop_coef(coef_in);
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    const auto groups = linop_groups(codes, C);
+    std::vector<Tensor> outs;
+    for (int64_t f : codes) {
+        std::vector<int64_t> shape{N};
+        for (int k = 0; f < DGS_VOLUME_FN_LAPLACIAN_TRACE && k < (int)f; ++k) shape.push_back(3);
+        shape.push_back(C);
+        outs.push_back(torch::zeros(shape, means.options()));
+    }
+    if (N == 0 || C == 0) return outs;
+    for (const auto &grp : groups) {
+        float *ptr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int mask = 0;
+        for (size_t i : grp) {
+            ptr[codes[i]] = outs[i].data_ptr<float>();
+            mask |= 1 << codes[i];
+        }
+        check(dgs_volume_forward_linop(mask, coef.data(), (int)P, (int)N, (int)C, means.data_ptr<float>(),
+                                       values.data_ptr<float>(), conics.data_ptr<float>(), samples.data_ptr<float>(),
+                                       binning.data_ptr(), (size_t)binning.numel(), ptr, as_dgs(cur_stream()),
+                                       debug ? 1 : 0),
+              "volume_forward_linop");
+    }
+    return outs;
+}
+
+std::tuple<Tensor, Tensor, Tensor> VolumeBackwardLinop(const std::vector<int64_t> &codes,
+                                                       const std::vector<double> &coef_in, const Tensor &means_in,
+                                                       const Tensor &values_in, const Tensor &conics_in,
+                                                       const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
+                                                       const Tensor &binning_in, const bool debug) {
+    TORCH_CHECK(dLs_in.size() == codes.size(), "one dL_dout per sampling function");
+    const auto coef = linop_coef(coef_in);
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    const auto groups = linop_groups(codes, C);
+    std::vector<Tensor> dLs;
+    for (size_t i = 0; i < codes.size(); ++i) {
+        dLs.push_back(f32(dLs_in[i], "dL_dout"));
+        TORCH_CHECK(dLs.back().numel() == N * linop_k(codes[i]) * C, "volume: dL_dout must be [N, components, C]");
+    }
+    Tensor dm = torch::zeros({P, 3}, means.options()), dv = torch::zeros({P, C}, means.options());
+    Tensor dc = torch::zeros({P, 6}, means.options());
+    if (P == 0 || C == 0) return std::make_tuple(dm, dv, dc);
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const float *ptr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int mask = 0;
+        for (size_t i : groups[gi]) {
+            ptr[codes[i]] = dLs[i].data_ptr<float>();
+            mask |= 1 << codes[i];
+        }
+        // (the call overwrites its gradients: the first group into the results, the others added)
+        Tensor gm = gi == 0 ? dm : torch::zeros_like(dm), gv = gi == 0 ? dv : torch::zeros_like(dv);
+        Tensor gc = gi == 0 ? dc : torch::zeros_like(dc);
+        const size_t ws = dgs_volume_workspace_size_linop(mask, (int)P, (int)N, (int)C, 1);
+        Tensor work = torch::empty({(int64_t)std::max<size_t>(ws, 4)}, means.options().dtype(torch::kUInt8));
+        check(dgs_volume_backward_linop(mask, coef.data(), (int)P, (int)N, (int)C, means.data_ptr<float>(),
+                                        values.data_ptr<float>(), conics.data_ptr<float>(), samples.data_ptr<float>(),
+                                        ptr, binning.data_ptr(), (size_t)binning.numel(), gm.data_ptr<float>(),
+                                        gv.data_ptr<float>(), gc.data_ptr<float>(), work.data_ptr(), ws,
+                                        as_dgs(cur_stream()), debug ? 1 : 0),
+              "volume_backward_linop");
+        if (gi > 0) {
+            dm.add_(gm);
+            dv.add_(gv);
+            dc.add_(gc);
+        }
+    }
+    return std::make_tuple(dm, dv, dc);
+}
+
+Tensor VolumeSamplesBackwardLinop(const std::vector<int64_t> &codes, const std::vector<double> &coef_in,
+                                  const Tensor &means_in, const Tensor &values_in, const Tensor &conics_in,
+                                  const Tensor &samples_in, const std::vector<Tensor> &dLs_in,
+                                  const Tensor &binning_in, const bool debug) {
+    TORCH_CHECK(dLs_in.size() == codes.size(), "one dL_dout per sampling function");
+    const auto coef = linop_coef(coef_in);
+    const Tensor means = f32(means_in, "means"), values = f32(values_in, "values");
+    const Tensor conics = f32(conics_in, "conics"), samples = f32(samples_in, "samples");
+    const Tensor binning = u8(binning_in, "binning_buffer");
+    vol_shapes(means, conics, samples);
+    TORCH_CHECK(values.dim() == 2 && values.size(0) == means.size(0), "volume: values must be [P, C]");
+    const int64_t P = means.size(0), N = samples.size(0), C = values.size(1);
+    const auto groups = linop_groups(codes, C);
+    std::vector<Tensor> dLs;
+    for (size_t i = 0; i < codes.size(); ++i) {
+        dLs.push_back(f32(dLs_in[i], "dL_dout"));
+        TORCH_CHECK(dLs.back().numel() == N * linop_k(codes[i]) * C, "volume: dL_dout must be [N, components, C]");
+    }
+    Tensor ds = torch::zeros({N, 3}, means.options());
+    if (N == 0 || P == 0 || C == 0) return ds;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const float *ptr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int mask = 0;
+        for (size_t i : groups[gi]) {
+            ptr[codes[i]] = dLs[i].data_ptr<float>();
+            mask |= 1 << codes[i];
+        }
+        Tensor part = gi == 0 ? ds : torch::empty({N, 3}, means.options());
+        Tensor work = torch::empty({4}, means.options().dtype(torch::kUInt8));  // (the size is 0 for every mask)
+        check(dgs_volume_backward_samples_linop(mask, coef.data(), (int)P, (int)N, (int)C, means.data_ptr<float>(),
+                                                values.data_ptr<float>(), conics.data_ptr<float>(),
+                                                samples.data_ptr<float>(), ptr, binning.data_ptr(),
+                                                (size_t)binning.numel(), part.data_ptr<float>(), work.data_ptr(), 0,
+                                                as_dgs(cur_stream()), debug ? 1 : 0),
+              "volume_samples_backward_linop");
+        if (gi > 0) ds.add_(part);
+    }
+    return ds;
+}
+
 std::tuple<int64_t, int64_t> VolumeCountPairs(const Tensor &means_in, const Tensor &conics_in,
                                               const Tensor &samples_in, const Tensor &binning_in) {
     const Tensor means = f32(means_in, "means"), conics = f32(conics_in, "conics");
@@ -1432,6 +1602,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("volume_forward_ops", &VolumeForwardOps);
     m.def("volume_backward_ops", &VolumeBackwardOps);
     m.def("volume_samples_backward_ops", &VolumeSamplesBackwardOps);
+    m.def("volume_forward_linop", &VolumeForwardLinop);
+    m.def("volume_backward_linop", &VolumeBackwardLinop);
+    m.def("volume_samples_backward_linop", &VolumeSamplesBackwardLinop);
     m.def("volume_count_pairs", &VolumeCountPairs);
     m.def("library_version", []() { return dgs_version(); });
     m.def("warmup", []() { check(dgs_warmup(as_dgs(cur_stream())), "warmup"); });

@@ -31,12 +31,110 @@ from . import _C, call_debug
 
 FUNCTION_CODES = {"gaussian": 0, "derivative": 1, "laplacian": 2, "third": 3, "laplacian_trace": 4}
 TRACE = FUNCTION_CODES["laplacian_trace"]
+OPERATOR = 5  # a LinearOperator instance in place of a name (DGS_VOLUME_FN_OPERATOR)
 
 
-def _multi_calls(codes):
-    """The forward, backward and sample-gradient bindings of a list of codes: the _ops ones
-    (dgs_volume_*_ops, five functions) only when the trace is among them, else the ones every
-    call without it has always taken."""
+class LinearOperator:
+    """A constant-coefficient linear operator of a D = 3 field,
+
+        L u = c0 u + sum_i b_i d_i u + sum_ij W_ij d_ij u,
+
+    sampled as ONE output [N, C] ("Linear operator"): a heat residual
+    LinearOperator(b=(0, 0, 1), W=LinearOperator.laplacian((0, 1), -kappa).W) of a field over
+    (x, y, t), a wave operator, anisotropic diffusion div(K grad u), Helmholtz.  An instance goes
+    wherever a function name does (`sample_volume`, `sample_volume_multi`,
+    `VolumeSampler.sample_gaussians_multi`, `VolumeSampler.sample_gaussians_operator`).  By
+    definition the output is c0 * gaussian + (b * derivative).sum + (W * laplacian).sum of this
+    package's outputs, with their sign conventions, at about the gaussian's cost.
+
+    `b` is three numbers; `W` a 3 x 3 nested sequence or tensor, symmetrised as (W + W^T) / 2, or six
+    packed numbers [w00, w01, w02, w11, w12, w22] (entries of the symmetric W).  The coefficients are
+    constants: they are kept as ten Python floats rounded to float32 (`coef`: c0, b, packed W) and
+    get no gradient; learnable coefficients combine the outputs of `sample_gaussians_multi`."""
+
+    def __init__(self, c0=0.0, b=None, W=None):
+        for x in (c0, b, W):
+            if isinstance(x, torch.Tensor) and x.requires_grad:
+                raise ValueError("LinearOperator takes constants: a coefficient tensor that requires a gradient is "
+                                 "not supported; combine the outputs of sample_gaussians_multi(\"gaussian\", "
+                                 "\"derivative\", \"laplacian\") instead")
+        c0 = torch.as_tensor(c0, dtype=torch.float64).reshape(())
+        b = torch.zeros(3, dtype=torch.float64) if b is None else torch.as_tensor(b, dtype=torch.float64).cpu()
+        W = torch.zeros(6, dtype=torch.float64) if W is None else torch.as_tensor(W, dtype=torch.float64).cpu()
+        if b.shape != (3,):
+            raise ValueError("LinearOperator: b is three numbers")
+        if W.shape == (3, 3):
+            W = (W + W.T) / 2
+            W = torch.stack([W[0, 0], W[0, 1], W[0, 2], W[1, 1], W[1, 2], W[2, 2]])
+        elif W.shape != (6,):
+            raise ValueError("LinearOperator: W is 3 x 3 or six packed numbers [w00, w01, w02, w11, w12, w22]")
+        coef = torch.cat([c0.cpu().reshape(1), b, W]).to(torch.float32)
+        if not bool(torch.isfinite(coef).all()):
+            raise ValueError("LinearOperator: the coefficients must be finite")
+        self.coef = [float(x) for x in coef.tolist()]
+
+    @property
+    def c0(self):
+        return self.coef[0]
+
+    @property
+    def b(self):
+        return tuple(self.coef[1:4])
+
+    @property
+    def W(self):
+        w = self.coef[4:]
+        return ((w[0], w[1], w[2]), (w[1], w[3], w[4]), (w[2], w[4], w[5]))
+
+    @classmethod
+    def laplacian(cls, axes=(0, 1, 2), scale=1.0):
+        """scale * sum of d_ii u over `axes` (axes=(0, 1): the space Laplacian of an (x, y, t) field)."""
+        return cls.diagonal(*[scale if i in axes else 0.0 for i in range(3)])
+
+    @classmethod
+    def diagonal(cls, w0, w1, w2):
+        """w0 d_00 u + w1 d_11 u + w2 d_22 u"""
+        return cls(W=[w0, 0.0, 0.0, w1, 0.0, w2])
+
+    def __repr__(self):
+        return f"LinearOperator(c0={self.c0}, b={self.b}, W={self.W})"
+
+
+class _Codes(tuple):
+    """The function codes of a call; `coef` holds the operator's coefficients when code 5 is among them."""
+    coef = None
+
+
+def _coef(codes):
+    return getattr(codes, "coef", None)  # (a plain tuple of codes holds no operator)
+
+
+def _parse(functions):
+    codes, coef = [], None
+    for f in functions:
+        if isinstance(f, LinearOperator):
+            if coef is not None:
+                raise ValueError("one LinearOperator per call (their coefficients are the call's); "
+                                 "sample the second one in a call of its own")
+            codes.append(OPERATOR)
+            coef = f.coef
+        else:
+            codes.append(FUNCTION_CODES[f] if isinstance(f, str) else int(f))
+            if codes[-1] == OPERATOR:
+                raise ValueError("function 5 is given as a LinearOperator instance")
+    codes = _Codes(codes)
+    codes.coef = coef
+    return codes
+
+
+def _multi_calls(codes, coef=None):
+    """The forward, backward and sample-gradient bindings of a list of codes: the _linop ones
+    (dgs_volume_*_linop, with the coefficients) only when the operator is among them, the _ops ones
+    (dgs_volume_*_ops, five functions) only when the trace is, else the ones every call without
+    either has always taken."""
+    if OPERATOR in codes:
+        return tuple((lambda cs, *a, _f=f: _f(cs, coef, *a)) for f in
+                     (_C.volume_forward_linop, _C.volume_backward_linop, _C.volume_samples_backward_linop))
     if TRACE in codes:
         return _C.volume_forward_ops, _C.volume_backward_ops, _C.volume_samples_backward_ops
     return _C.volume_forward_multi, _C.volume_backward_multi, _C.volume_samples_backward
@@ -100,7 +198,10 @@ def sample_volume(function, means, values, conics, samples, binning, debug=False
     Poisson, wave or Navier-Stokes residual uses of the [N, 3, 3, C] Hessian, at about the
     gaussian's cost ("Trace Laplacian").  sample_grad=True also
     returns the gradient of `samples` when they require one (one more walk of the candidates, about
-    a forward's time; without the flag such samples raise NotImplementedError)."""
+    a forward's time; without the flag such samples raise NotImplementedError).  A LinearOperator
+    instance in place of the name samples that operator, [N, C]."""
+    if isinstance(function, LinearOperator):
+        return sample_volume_multi((function,), means, values, conics, samples, binning, debug, sample_grad)[0]
     code = FUNCTION_CODES[function] if isinstance(function, str) else int(function)
     if code == TRACE:  # (the per-function bindings keep refusing it: the _ops ones take it)
         return sample_volume_multi((code,), means, values, conics, samples, binning, debug, sample_grad)[0]
@@ -114,7 +215,7 @@ class _SampleVolumeMulti(torch.autograd.Function):
         if ctx.needs_input_grad[4]:
             raise NotImplementedError("VolumeSampler returns no gradient for samples; detach them "
                                       "(or ask for it: sample_grad=True)")
-        outs = call_debug(_multi_calls(codes)[0], debug, "vol_multi_fw", list(codes), means, values, conics,
+        outs = call_debug(_multi_calls(codes, _coef(codes))[0], debug, "vol_multi_fw", list(codes), means, values, conics,
                           samples, binning, debug)
         ctx.codes, ctx.debug = codes, debug
         ctx.save_for_backward(means, values, conics, samples, binning)
@@ -127,7 +228,7 @@ class _SampleVolumeMulti(torch.autograd.Function):
         if not live:
             return (None,) * 7
         live_codes = [c for c, _ in live]
-        gm, gv, gc = call_debug(_multi_calls(live_codes)[1], ctx.debug, "vol_multi_bw", live_codes,
+        gm, gv, gc = call_debug(_multi_calls(live_codes, _coef(ctx.codes))[1], ctx.debug, "vol_multi_bw", live_codes,
                                 means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
         return None, gm, gv, gc, None, None, None
 
@@ -138,7 +239,7 @@ class _SampleVolumeMultiSG(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, codes, means, values, conics, samples, binning, debug):
-        outs = call_debug(_multi_calls(codes)[0], debug, "vol_multi_fw", list(codes), means, values, conics,
+        outs = call_debug(_multi_calls(codes, _coef(codes))[0], debug, "vol_multi_fw", list(codes), means, values, conics,
                           samples, binning, debug)
         ctx.codes, ctx.debug = codes, debug
         ctx.save_for_backward(means, values, conics, samples, binning)
@@ -152,7 +253,7 @@ class _SampleVolumeMultiSG(torch.autograd.Function):
             return (None,) * 7
         gm = gv = gc = gs = None
         live_codes = [c for c, _ in live]
-        _, bwd, sgrad = _multi_calls(live_codes)
+        _, bwd, sgrad = _multi_calls(live_codes, _coef(ctx.codes))
         if any(ctx.needs_input_grad[1:4]):
             gm, gv, gc = call_debug(bwd, ctx.debug, "vol_multi_bw", live_codes,
                                     means, values, conics, samples, [g for _, g in live], binning, ctx.debug)
@@ -172,8 +273,13 @@ def sample_volume_multi(functions, means, values, conics, samples, binning, debu
     per-function kernels run in turn and their gradients are added.  Each output is bitwise the one
     `sample_volume` returns.  An output whose gradient is None is left out of the backward.
     sample_grad=True: as for `sample_volume`, the gradient of `samples` over the live outputs (one
-    walk up to C = 4, the per-function calls added above)."""
-    codes = tuple(FUNCTION_CODES[f] if isinstance(f, str) else int(f) for f in functions)
+    walk up to C = 4, the per-function calls added above).
+
+    One of `functions` may be a LinearOperator (dgs_volume_*_linop): with "gaussian" and / or
+    "derivative" up to C = 4 it shares their walk (what a Burgers-type residual needs: u, grad u and
+    u_t - nu u_xx); asked together with "laplacian", "third" or "laplacian_trace" it runs as its own
+    call beside the fused rest; two operators raise ValueError."""
+    codes = _parse(functions)
     fn = _SampleVolumeMultiSG if sample_grad else _SampleVolumeMulti
     return fn.apply(codes, means, values, conics, samples, binning, debug)
 
@@ -224,8 +330,8 @@ class VolumeSampler:
                              self.debug, self.sample_grad)
 
     def sample_gaussians_multi(self, *functions):
-        """Several functions ("gaussian", "derivative", "laplacian", "third", "laplacian_trace" or 0..4) in one
-        call; returns a tuple in the order asked (sample_volume_multi: one walk of the candidates
+        """Several functions ("gaussian", "derivative", "laplacian", "third", "laplacian_trace" or 0..4,
+        or one LinearOperator instance) in one call; returns a tuple in the order asked (sample_volume_multi: one walk of the candidates
         for fields of up to four channels)."""
         self._rebin_if_changed()
         return sample_volume_multi(functions, self.means, self.values, self.conics, self.samples,
@@ -246,3 +352,9 @@ class VolumeSampler:
     def sample_gaussians_laplacian_trace(self):
         """The trace of the laplacian, [N, C] (one value per channel)."""
         return self._run(TRACE)
+
+    def sample_gaussians_operator(self, op):
+        """The LinearOperator `op` of the field, [N, C] (one value per channel)."""
+        if not isinstance(op, LinearOperator):
+            raise TypeError("sample_gaussians_operator takes a LinearOperator")
+        return self._run(op)

@@ -178,6 +178,65 @@ int dgs_volume_backward_samples_ops(int mask, int P, int N, int C, const float *
                                     const void *binning, size_t binning_bytes, float *dL_dsamples,
                                     void *workspace, size_t workspace_bytes, dgs_stream_t stream, int debug);
 
+/* A sixth function, a constant-coefficient linear operator of the field ("Linear
+ * operator"): code 5, bit 5 of a mask,
+ *   L u = c0 u + sum_i b_i d_i u + sum_ij W_ij d_ij u,   W symmetric,
+ *   coef[10] = [c0, b0, b1, b2, w00, w01, w02, w11, w12, w22]   (w packed like a conic, w_ij the
+ *   entry of W; an off-diagonal entry counts twice in W:H),
+ *   out[N][C],  out[n][ch] = sum_g v_g,ch G t,
+ * over the pair set, wrap and exact-zero skip of the other functions.  With k_u = m_u w_u (m_u = 1
+ * on the diagonal, 2 off it, formed on the host, exact) t is evaluated in fp32 without contraction
+ * in exactly this order, every sum left to right:
+ *   lin = b0 a0 + b1 a1 + b2 a2
+ *   q   = k00 (a0 a0 - c00) + k01 (a0 a1 - c01) + k02 (a0 a2 - c02)
+ *       + k11 (a1 a1 - c11) + k12 (a1 a2 - c12) + k22 (a2 a2 - c22)
+ *   t   = (c0 + lin) + q
+ * By definition the output is c0 gaussian + sum_i b_i derivative[i] + sum_ij W_ij laplacian[i][j]
+ * of this library's own outputs, with their sign conventions; it rounds differently and is not
+ * bitwise that combination.  In the gradients phi = h t, d phi / d a_i = h (b_i + 2 sum_j W_ij a_j),
+ * d phi / d c_u = -h k_u.  The forward sum is written out as the trace's: among the binned
+ * Gaussians fma(round(v G), t, acc); among the others round(acc + round(round(v G) t)) at C = 1
+ * and the same fma at C > 1.  So an output of a mask with the operator is bit-identical to the
+ * mask-32 call's at the same C.
+ *
+ * The coefficients are constants of one call: coef is a HOST pointer to ten floats, read during the
+ * call and not needed afterwards; they reach the kernels as launch arguments, so two calls on one
+ * binning with different coefficients each see their own.  There is no gradient with respect to
+ * them.
+ *
+ * The *_linop entries take the argument lists of the *_ops entries after (mask, coef), with outs /
+ * dL_douts arrays of SIX pointers (indexed by function code; entries outside the mask ignored).
+ * Valid masks are 1..63; bit 5 excludes bits 2, 3 and 4 (DGS_ERR_ARG, "mask", otherwise).
+ *   - mask < 32: the call is the *_ops entry itself (the same checks, the same launches,
+ *     bit-identical results; coef may be NULL and the sixth pointer is not read);
+ *   - mask 32: any C (C > 1 in channel blocks of 4 and 8, as the trace);
+ *   - the operator with the gaussian and / or the derivative (masks 33, 34, 35): one walk of the
+ *     candidates at 1 <= C <= DGS_VOLUME_FUSED_MAX_C; above it DGS_ERR_ARG (call per function and
+ *     add) and a workspace size of 0;
+ *   - bit 5 with a NULL coef or a non-finite coefficient: DGS_ERR_ARG ("coef") before any device
+ *     work.
+ * Backward workspace: N * (unique components of the mask, 1 for the operator) * C * 4 bytes; the
+ * forward and the sample gradient need none.  Edge sizes, the stale buffer / changed input guard,
+ * DGS_ERR_BUFFER for a missing or short binning and the ordering of calls on one binning are those
+ * of the *_ops calls; no atomics, no host sync, no allocation.  New exported functions only:
+ * DGS_ABI_VERSION is unchanged, and the entries above keep refusing bit 5. */
+#define DGS_VOLUME_FN_OPERATOR 5
+size_t dgs_volume_workspace_size_linop(int mask, int P, int N, int C, int backward);
+int dgs_volume_forward_linop(int mask, const float *coef, int P, int N, int C, const float *means,
+                             const float *values, const float *conics, const float *samples,
+                             const void *binning, size_t binning_bytes, float *const *outs,
+                             dgs_stream_t stream, int debug);
+int dgs_volume_backward_linop(int mask, const float *coef, int P, int N, int C, const float *means,
+                              const float *values, const float *conics, const float *samples,
+                              const float *const *dL_douts, const void *binning, size_t binning_bytes,
+                              float *dL_dmeans, float *dL_dvalues, float *dL_dconics, void *workspace,
+                              size_t workspace_bytes, dgs_stream_t stream, int debug);
+int dgs_volume_backward_samples_linop(int mask, const float *coef, int P, int N, int C, const float *means,
+                                      const float *values, const float *conics, const float *samples,
+                                      const float *const *dL_douts, const void *binning,
+                                      size_t binning_bytes, float *dL_dsamples, void *workspace,
+                                      size_t workspace_bytes, dgs_stream_t stream, int debug);
+
 /* Diagnostic (not on any reference API): counts[0] = pairs the forward evaluates (candidates
  * inside their own cut box), counts[1] = live pairs (G = expf(power) > 0).  Host, syncs;
  * DGS_ERR_BUFFER when the inputs differ from the binned ones. */

@@ -410,3 +410,68 @@ def volume_samples_backward_fused(codes, means, values, conics, samples, dLs, bi
     _check(fn(mask, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
               binning.numel(), _ptr(ds), None, 0, _stream(), int(bool(debug))))
     return ds
+
+
+# the *_linop entries (six functions: code 5 is the constant-coefficient linear operator, [N, C], with
+# its ten coefficients [c0, b0, b1, b2, w00, w01, w02, w11, w12, w22] as a host array of the call)
+_PP6 = ctypes.c_void_p * 6
+_F10 = ctypes.c_float * 10
+_lib.dgs_volume_workspace_size_linop.restype = _SZ
+_lib.dgs_volume_workspace_size_linop.argtypes = [_I] * 5
+_lib.dgs_volume_forward_linop.argtypes = [_I, _P] + [_I] * 3 + [_P] * 4 + [_P, _SZ, _PP6, _P, _I]
+_lib.dgs_volume_backward_linop.argtypes = [_I, _P] + [_I] * 3 + [_P] * 4 + [_PP6, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _I]
+_lib.dgs_volume_backward_samples_linop.argtypes = [_I, _P] + [_I] * 3 + [_P] * 4 + [_PP6, _P, _SZ, _P, _P, _SZ, _P, _I]
+VOLUME_OPERATOR = 5
+
+
+def _linop_args(codes, coef, by_code):
+    mask = sum(1 << c for c in codes)
+    ptrs = _PP6(*[by_code[c].data_ptr() if c in by_code else None for c in range(6)])
+    return mask, (None if coef is None else _F10(*coef)), ptrs
+
+
+def volume_workspace_size_linop(mask, P, N, C, backward):
+    return _lib.dgs_volume_workspace_size_linop(mask, P, N, C, backward)
+
+
+def volume_forward_linop(codes, coef, means, values, conics, samples, binning, debug):
+    """Outputs of the functions `codes` (0..5, each once) in the order given, through
+    dgs_volume_forward_linop; coef: ten numbers, or None without code 5."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    outs = {c: torch.zeros((N, C) if c >= VOLUME_TRACE else _vol_shape(N, c, C), device=means.device) for c in codes}
+    mask, cf, ptrs = _linop_args(codes, coef, outs)
+    _check(_lib.dgs_volume_forward_linop(
+        mask, cf, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), _ptr(binning), binning.numel(), ptrs,
+        _stream(), int(bool(debug))))
+    return [outs[c] for c in codes]
+
+
+def volume_backward_linop(codes, coef, means, values, conics, samples, dLs, binning, debug, workspace=None):
+    """Gradients (dmeans, dvalues, dconics) of sum_f <dLs[f], out_f> through dgs_volume_backward_linop."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    dLs = {c: _f32(d) for c, d in zip(codes, dLs)}
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    dm, dv, dc = (torch.zeros(P, k, device=means.device) for k in (3, C, 6))
+    mask, cf, ptrs = _linop_args(codes, coef, dLs)
+    if workspace is None:
+        workspace = torch.empty(_lib.dgs_volume_workspace_size_linop(mask, P, N, C, 1), dtype=torch.uint8,
+                                device=means.device)
+    _check(_lib.dgs_volume_backward_linop(
+        mask, cf, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
+        binning.numel(), _ptr(dm), _ptr(dv), _ptr(dc), _ptr(workspace), workspace.numel(), _stream(),
+        int(bool(debug))))
+    return dm, dv, dc
+
+
+def volume_samples_backward_linop(codes, coef, means, values, conics, samples, dLs, binning, debug):
+    """dL/dsamples [N, 3] of sum_f <dLs[f], out_f> through dgs_volume_backward_samples_linop."""
+    means, values, conics, samples = map(_f32, (means, values, conics, samples))
+    dLs = {c: _f32(d) for c, d in zip(codes, dLs)}
+    P, N, C = means.shape[0], samples.shape[0], values.shape[1]
+    ds = torch.zeros(N, 3, device=means.device)
+    mask, cf, ptrs = _linop_args(codes, coef, dLs)
+    _check(_lib.dgs_volume_backward_samples_linop(
+        mask, cf, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
+        binning.numel(), _ptr(ds), None, 0, _stream(), int(bool(debug))))
+    return ds

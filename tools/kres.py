@@ -29,6 +29,6 @@ names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), ca
 for r, n in zip(rows, names):
     if filt not in n or "hipcub" in n or "rocprim" in n:
         continue
-    print(f"{n[:90]:90s} V{r.get('VGPRs', '?'):>4s} A{r.get('AGPRs', '?'):>3s} "
+    print(f"{n[:90]:90s} V{r.get('VGPRs', '?'):>4s} A{r.get('AGPRs', '?'):>3s} S{r.get('TotalSGPRs', '?'):>4s} sspill{r.get('SGPRs Spill', '?'):>3s} "
           f"scr{r.get('ScratchSize [bytes/lane]', '?'):>4s} occ{r.get('Occupancy [waves/SIMD]', '?'):>2s} "
           f"lds{r.get('LDS Size [bytes/block]', '?')}")

@@ -2,6 +2,7 @@
 
     python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
                                        [--rounds 3] [--steps 3] [--C 3] [--separate-only] [--trace-vs-hessian]
+                                       [--operator-vs-multi]
 
 The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice; C = 1 unless --C).  After settle
 steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
@@ -19,6 +20,17 @@ times in alternation the call as given (`fused_ms`, also `trace_ms`) against wha
 trace does (`separate_ms`, also `hessian_ms`): the same call with "laplacian" in its place, followed
 by `out.diagonal(dim1=1, dim2=2).sum(-1)`; both are forward + backward from the same upstream
 gradients.  `single_ms` then holds the other functions' single calls and the laplacian's.
+
+--operator-vs-multi (--functions is not used): the heat operator u_t - kappa (u_xx + u_yy) of an
+(x, y, t) field, kappa = 0.01, forward + backward over one binning, timed in alternation as
+  route      what a user without LinearOperator does: sample_gaussians_multi("gaussian", "derivative",
+             "laplacian") and the contraction in torch, the loss on the residual (`separate_ms`)
+  route_gdr  the same with the loss on the gaussian, the derivative and the residual
+  operator   sample_gaussians_operator(heat), the loss on it (`fused_ms`)
+  op_gd      sample_gaussians_multi("gaussian", "derivative", heat), the loss on all three
+and the single calls gaussian, derivative, laplacian, laplacian_trace; all in `single_ms`.  In a
+package from before LinearOperator only the routes and the single calls run (the yardstick of an A/B
+run through tools/ab.py --script against a build of the parent commit).
 """
 import argparse
 import json
@@ -46,6 +58,7 @@ def main():
     ap.add_argument("--settle", type=int, default=2)
     ap.add_argument("--separate-only", action="store_true")
     ap.add_argument("--trace-vs-hessian", action="store_true")
+    ap.add_argument("--operator-vs-multi", action="store_true")
     ap.add_argument("--C", type=int, default=1, help="channels")
     args = ap.parse_args()
     C = args.C
@@ -59,6 +72,8 @@ def main():
     vs = VolumeSampler(False)
     vs.preprocess(means, values, covs, conics, samples)
     gen = torch.Generator().manual_seed(5)
+    if args.operator_vs_multi:
+        return operator_vs_multi(args, vs, (means, values, conics), N, C, gen, dev)
     order = {"laplacian_trace": 0}  # (its output is [N, C])
     w = {f: torch.randn((N,) + (3,) * order.get(f, FUNCTION_CODES[f]) + (C,), generator=gen).to(dev) for f in fns}
     single = {"gaussian": vs.sample_gaussians, "derivative": vs.sample_gaussians_derivative,
@@ -144,6 +159,60 @@ def trace_vs_hessian(args, vs, fns, w, single, params, N):
                       "fused_ms": med["trace"], "separate_ms": med["hessian"], "speedup": med["hessian"] / med["trace"],
                       "trace_rounds_ms": times["trace"], "hessian_rounds_ms": times["hessian"],
                       "single_ms": {f: med[f] for f in others}}), flush=True)
+
+
+def operator_vs_multi(args, vs, params, N, C, gen, dev):
+    kappa = 0.01
+    try:
+        from diff_gaussian_sampling.volume import LinearOperator
+        heat = LinearOperator(b=(0.0, 0.0, 1.0), W=LinearOperator.laplacian((0, 1), -kappa).W)
+    except ImportError:  # a package from before the operator: the routes and the single calls only
+        heat = None
+    w = {f: torch.randn((N,) + (3,) * k + (C,), generator=gen).to(dev) for f, k in (("g", 0), ("d", 1), ("r", 0))}
+    single = {"gaussian": vs.sample_gaussians, "derivative": vs.sample_gaussians_derivative,
+              "laplacian": vs.sample_gaussians_laplacian}
+    if hasattr(vs, "sample_gaussians_laplacian_trace"):
+        single["laplacian_trace"] = vs.sample_gaussians_laplacian_trace
+
+    def step(which):
+        for t in params:
+            t.grad = None
+        if which in ("route", "route_gdr"):
+            g, d, lap = vs.sample_gaussians_multi("gaussian", "derivative", "laplacian")
+            r = d[:, 2] - kappa * (lap[:, 0, 0] + lap[:, 1, 1])
+            outs, ws = ([r], [w["r"]]) if which == "route" else ([g, d, r], [w["g"], w["d"], w["r"]])
+        elif which == "operator":
+            outs, ws = [vs.sample_gaussians_operator(heat)], [w["r"]]
+        elif which == "op_gd":
+            outs, ws = list(vs.sample_gaussians_multi("gaussian", "derivative", heat)), [w["g"], w["d"], w["r"]]
+        else:
+            o = single[which]()
+            return o.backward(torch.ones_like(o))
+        torch.autograd.backward(outs, ws)
+
+    def timed(which):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(which)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+
+    kinds = ["route", "route_gdr"] + (["operator", "op_gd"] if heat is not None else []) + list(single)
+    for k in kinds[:4]:
+        for _ in range(args.settle):
+            step(k)
+    times = {k: [] for k in kinds}
+    for _ in range(args.rounds):
+        for k in kinds:
+            times[k].append(timed(k))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    res = {"P": args.P, "N": N, "C": C, "grid3": args.grid3, "mode": "operator-vs-multi", "rounds": args.rounds,
+           "steps": args.steps, "separate_ms": med["route"], "single_ms": med, "rounds_ms": times}
+    if heat is not None:
+        res.update(fused_ms=med["operator"], speedup=med["route"] / med["operator"],
+                   speedup_gd=med["route_gdr"] / med["op_gd"])
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ clock drift and the box hit every kind alike).
                                              [--C 3] [--kinds sg:gaussian+derivative+laplacian] [--pkgs base,variants/NAME]
 
 Kinds: sg:<function>, sg:all (mask 15) and sg:<f>+<g>+... (that mask; laplacian_trace among the names
-takes the _ops binding) -- the new call, whole (the
+takes the _ops binding, heat -- a LinearOperator, code 5 -- the _linop one) -- the new call, whole (the
 input check and the kernels); fwd:<function> -- the forward call on the same binning.  --C sets the
 channel count (several functions share one walk up to C = 4; above, the per-function calls are added).
 --pkgs times every kind under several packages in turn (base: the in-tree one; variants/NAME: a
@@ -50,11 +50,15 @@ def child(a):
         code = FUNCS.index(f)
         call = lambda: dgs._C.volume_forward(code, means, values, conics, samples, buf, False)  # noqa: E731
     else:
-        codes = [0, 1, 2, 3] if f == "all" else [(FUNCS + ["laplacian_trace"]).index(x) for x in f.split("+")]
+        codes = [0, 1, 2, 3] if f == "all" else [(FUNCS + ["laplacian_trace", "heat"]).index(x) for x in f.split("+")]
         gen = torch.Generator().manual_seed(5)
-        dLs = [torch.randn((N, 1 if k == 4 else 3 ** k, a.C), generator=gen).to(dev) for k in codes]
+        dLs = [torch.randn((N, 1 if k >= 4 else 3 ** k, a.C), generator=gen).to(dev) for k in codes]
         sg = dgs._C.volume_samples_backward_ops if 4 in codes else dgs._C.volume_samples_backward
         call = lambda: sg(codes, means, values, conics, samples, dLs, buf, False)  # noqa: E731
+        if 5 in codes:  # the heat operator u_t - 0.01 (u_xx + u_yy): the _linop binding with its coefficients
+            heat = [0.0, 0.0, 0.0, 1.0, -0.01, 0.0, 0.0, -0.01, 0.0, 0.0]
+            call = lambda: dgs._C.volume_samples_backward_linop(codes, heat, means, values, conics, samples, dLs,  # noqa: E731
+                                                                buf, False)
     for _ in range(a.warmup):
         call()
     torch.cuda.synchronize()
