@@ -15,6 +15,10 @@
 //     every pair with a non-zero contribution has |wrap(x)| = |x - 2k| <= r for its own image k.
 //     (A pair kept under an image that is not its own has |wrap(x)| > 1.5: G is exactly 0.
 //     pair_eval always applies the reference's wrap, so its value never depends on the window.)
+//   * an axis may be open instead (dgs_volume_preprocess_axes; Hdr::open, DESIGN.md 4.8, "Open
+//     axes"): the walks visit its direct image only, whose cut box test is already the one on the
+//     raw distance (and inside a cut box the wrap is the identity), and the loops over the big
+//     Gaussians leave its X_d unwrapped (pair_eval with Axes); nothing else knows about it;
 //   * "big" Gaussians (everything else) sit in one extra cell and meet every sample;
 //   * forward: lane = sample (in cell order), outputs summed in registers, no atomics;
 //     backward: lane = Gaussian (in cell order) walking the samples of its images, gradients
@@ -42,6 +46,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <type_traits>
 
 #include "dgs.h"
@@ -65,11 +70,25 @@ struct Hdr {
     float lo[3], cs[3], E[3];
     float split;     // small Gaussians with every cut half-width <= split: class 0, else class 1
     float Ec[2][3];  // per class, the largest cut half-width per axis (the window reach)
+    // bit d: axis d is open (dgs_volume_preprocess_axes): X_d is not wrapped and only the direct
+    // image exists.  The open mask and not the periodic one, so that 0 is the all-periodic torus.
+    // (In the four bytes that padded the offsets: the header, which k_vol_backward copies, keeps its size.)
+    int open;
     int64_t o_gext, o_gids, o_sids, o_gstart, o_sstart, o_gpk, o_gek;
     int64_t o_mcopy, o_ccopy, o_scopy, o_flag;  // the binned tensors; flag = they differ from the call's
 };
 constexpr size_t kHdrBytes = 256;
 static_assert(sizeof(Hdr) <= kHdrBytes, "volume header too large");
+static_assert(sizeof(Hdr) == 192, "Hdr::open belongs in the padding before the offsets");
+// What the kernels read of the axes, as data behind the header (Hdr keeps its size: k_vol_backward
+// copies it): no kernel tests Hdr::open.  The image ranges of an axis are derived from the grid's
+// extent [ilo, ihi] (image_range); an open axis has the empty extent [+inf, -inf], from which no
+// image but the direct one can be reached, so the walks skip its images with the arithmetic they
+// had.  lim: the wrap's limit for the pairs of the big Gaussians (Axes).
+struct HdrAx {
+    float ilo[3], ihi[3], lim[3];
+};
+static_assert(sizeof(Hdr) + sizeof(HdrAx) <= kHdrBytes, "volume header too large");
 
 static inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -171,17 +190,34 @@ __host__ __device__ constexpr int u3i(int u, int w) {
     return 0;
 }
 
-__device__ __forceinline__ float wrap1(float x) {  // forward.cu:149-157, one axis
+// The axes a pair is evaluated under.  Torus: every axis wraps (forward.cu:149-157), the parent's
+// arithmetic with nothing added; it serves every pair of the walks, on open axes too, because a
+// walk visits only the direct image of an open axis and keeps a pair only inside its cut box,
+// |m - s| <= r + 1e-5 with r <= kMaxReach < 1, where the wrap is the identity.  Axes: the binning's
+// Hdr::open, for the pairs of the big Gaussians, which meet every sample at any distance: an open
+// axis is not wrapped.  So the hot loops of the walks hold no register for the axes: their kernels
+// already take every scalar register there is, and one more live scalar costs a lane read per use.
+struct Torus {};
+struct Axes {
+    float lim[3];  // |x| above it wraps: 1 on a periodic axis, +inf on an open one (HdrAx::lim)
+};
+__device__ __forceinline__ float wrap_axis(const Torus &, int, float x) {
     if (fabsf(x) > 1.0f) x = x >= 0.0f ? fmodf(x, 2.0f) - 2.0f : fmodf(x, 2.0f) + 2.0f;
     return x;
 }
-// One pair: wrapped X, power (exact operation order of include/dgs_volume.h, no contraction,
-// so that the numpy oracle reproduces it bit for bit), G and a = A X.  False: power > 0 (the
-// reference's skip) or G == +0 (the pair adds exactly nothing; half of the cut box's pairs).
-__device__ __forceinline__ bool pair_eval(const float *m, const float *s, const float *c, float *X,
+__device__ __forceinline__ float wrap_axis(const Axes &ax, int d, float x) {
+    if (fabsf(x) > ax.lim[d]) x = x >= 0.0f ? fmodf(x, 2.0f) - 2.0f : fmodf(x, 2.0f) + 2.0f;
+    return x;
+}
+// One pair: wrapped X (open axes: not wrapped), power (exact operation order of
+// include/dgs_volume.h, no contraction, so that the numpy oracle reproduces it bit for bit), G and
+// a = A X.  False: power > 0 (the reference's skip) or G == +0 (the pair adds exactly nothing; half
+// of the cut box's pairs).
+template <class AX>
+__device__ __forceinline__ bool pair_eval(const AX &ax, const float *m, const float *s, const float *c, float *X,
                                           float &G, float *a) {
     DGS_NO_CONTRACT
-    for (int d = 0; d < 3; ++d) X[d] = wrap1(m[d] - s[d]);
+    for (int d = 0; d < 3; ++d) X[d] = wrap_axis(ax, d, m[d] - s[d]);
     const float qd = c[0] * X[0] * X[0] + c[3] * X[1] * X[1] + c[5] * X[2] * X[2];
     const float qo = c[1] * X[0] * X[1] + c[2] * X[0] * X[2] + c[4] * X[1] * X[2];
     const float power = -0.5f * qd - qo;
@@ -306,6 +342,15 @@ __device__ __forceinline__ void image_window(int k, float r, float &xa, float &x
 }
 
 __device__ __forceinline__ const Hdr &hdr_of(const char *buf) { return *reinterpret_cast<const Hdr *>(buf); }
+__device__ __forceinline__ const HdrAx &hax_of(const char *buf) { return *reinterpret_cast<const HdrAx *>(buf + sizeof(Hdr)); }
+// The wrap limits, read where the loops over the big Gaussians start (a volatile read: a plain one
+// is hoisted out of the loop over the cells and the three values then live through the walks, whose
+// kernels have no scalar register to spare).
+__device__ __forceinline__ Axes axes_of(const char *buf) {
+    const volatile int *l = reinterpret_cast<const volatile int *>(hax_of(buf).lim);
+    const auto uni = [](int bits) { return __int_as_float(__builtin_amdgcn_readfirstlane(bits)); };  // (wave-uniform)
+    return {{uni(l[0]), uni(l[1]), uni(l[2])}};
+}
 
 // ------------------------------------------------------------------------------ preprocess
 struct Red {
@@ -521,8 +566,11 @@ __global__ void k_vol_flag_read(int P, int N, const char *buf, unsigned long lon
     if (threadIdx.x == 0) out[0] = vol_stale(buf, hdr_of(buf), P, N) ? 1ull : 0ull;
 }
 
-__global__ void k_vol_header(Hdr h, char *buf) {
-    if (threadIdx.x == 0) *reinterpret_cast<Hdr *>(buf) = h;
+__global__ void k_vol_header(Hdr h, HdrAx hx, char *buf) {
+    if (threadIdx.x == 0) {
+        *reinterpret_cast<Hdr *>(buf) = h;
+        *reinterpret_cast<HdrAx *>(buf + sizeof(Hdr)) = hx;
+    }
 }
 
 // ------------------------------------------------------------------------------ the walks
@@ -538,11 +586,11 @@ __device__ __forceinline__ Bin bin_of(const char *buf, const Hdr &h) {
             reinterpret_cast<const float4 *>(buf + h.o_gpk),     reinterpret_cast<const float4 *>(buf + h.o_gek)};
 }
 
-// Images of one axis that a box [pl, ph] of points with reach r can meet inside the grid.
-__device__ __forceinline__ Win box_images(const Hdr &h, int d, float pl, float ph, float r, bool target_is_mean) {
-    const float ghi = h.lo[d] + h.cs[d] * h.n[d];
-    const Win wa = image_range(pl, r, h.lo[d], ghi, target_is_mean);
-    const Win wb = image_range(ph, r, h.lo[d], ghi, target_is_mean);
+// Images of one axis that a box [pl, ph] of points with reach r can meet inside the grid's extent
+// (HdrAx: an open axis has the direct one only).
+__device__ __forceinline__ Win box_images(const HdrAx &hx, int d, float pl, float ph, float r, bool target_is_mean) {
+    const Win wa = image_range(pl, r, hx.ilo[d], hx.ihi[d], target_is_mean);
+    const Win wb = image_range(ph, r, hx.ilo[d], hx.ihi[d], target_is_mean);
     return {min(wa.k0, wb.k0), max(wa.k1, wb.k1)};
 }
 // One axis of a window: the cells [c0, c1] that the targets of the box [pl, ph] under image k and
@@ -591,7 +639,7 @@ struct VCand {
 // Gaussians: fill(v, g) sets the staged candidate's values v[CB] of Gaussian g, and
 // eval(m, c, v) takes a candidate (mean, conic, staged values) that the lane keeps.
 template <int CB, class Fill, class Eval>
-__device__ __forceinline__ void walk_candidates(const Hdr &h, const Bin &bin, const float *__restrict__ conics,
+__device__ __forceinline__ void walk_candidates(const Hdr &h, const HdrAx &hx, const Bin &bin, const float *__restrict__ conics,
                                                 VCand<CB> *cand, int lane, const int *cc, bool active,
                                                 const float *s, Fill fill, Eval eval) {
     if (h.nsmall <= 0) return;
@@ -611,7 +659,7 @@ __device__ __forceinline__ void walk_candidates(const Hdr &h, const Bin &bin, co
         }
         bl[d] = fmaxf(bl[d], mn);
         bh[d] = fminf(bh[d], mx);
-        w[d] = box_images(h, d, bl[d], bh[d], h.E[d], true);
+        w[d] = box_images(hx, d, bl[d], bh[d], h.E[d], true);
     }
     for (int cls = 0; cls < 2; ++cls)  // per class: its own reach
     for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
@@ -699,14 +747,14 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
             auto values_of = [&](float *vr, int g) {
                 for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
             };
-            auto eval = [&](const float *m, const float *c, const float *vr) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, const float *vr) {
                 float X[3], a[3], G, t[KU];
                 if constexpr (COUNT) {
                     ++n_cand;
-                    if (pair_eval(m, s, c, X, G, a)) ++n_live;
+                    if (pair_eval(ax, m, s, c, X, G, a)) ++n_live;
                     return;
                 }
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 if constexpr (FN == kFnTrace) {  // no legacy bits to keep: the written-out sum (fwd_acc_c)
                     fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc);
                     return;
@@ -721,15 +769,17 @@ __global__ __launch_bounds__(kWave) void k_vol_forward(const char *__restrict__ 
                     for (int u = 0; u < KU; ++u) acc[u][ch] += v * G * t[u];
                 }
             };
-            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            walk_candidates<CB>(h, hax_of(buf), bin, conics, cand, lane, cc, active, s, values_of,
+                                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6], vr[CB];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
                     values_of(vr, g);
-                    eval(m, c, vr);
+                    eval(ax, m, c, vr);
                 }
                 if constexpr (COUNT) {
                     atomicAdd(&counts[0], n_cand);
@@ -765,13 +815,13 @@ __global__ __launch_bounds__(kBlock) void k_vol_hsum(int N, int C, const float *
 // (global).  CB == 1 means C == 1 (the big Gaussians): phi, g and e are
 // linear in h v0, so the pair uses h alone and the caller scales the mean / conic sums by v0 once
 // (bwd_store's scale).
-template <int FN, int CB>
-__device__ __forceinline__ void bwd_pair(const float *m, const float *c, const float *__restrict__ values, int g,
+template <int FN, int CB, class AX>
+__device__ __forceinline__ void bwd_pair(const AX &ax, const float *m, const float *c, const float *__restrict__ values, int g,
                                          int C, int cbase, int nch, const float *s, const float *hrow,
                                          float *dm, float *dc, float *dv, const float *cf = nullptr) {
     constexpr int KU = VTr<FN>::KU;
     float X[3], a[3], G, t[KU];
-    if (!pair_eval(m, s, c, X, G, a)) return;
+    if (!pair_eval(ax, m, s, c, X, G, a)) return;
     terms<FN>(a, c, t, cf);
     float hv[KU];
     if constexpr (CB == 1) {
@@ -901,11 +951,11 @@ __device__ __forceinline__ void vol_mom_add(float G, float phi, const float *g, 
     }
 }
 
-template <int FN>
-__device__ __forceinline__ void bwd_pair_t(const float *m, const float *c, const float *c2, const float *s,
+template <int FN, class AX>
+__device__ __forceinline__ void bwd_pair_t(const AX &ax, const float *m, const float *c, const float *c2, const float *s,
                                            const float *H, VMom &M) {
     float X[3], a[3], G;
-    if (!pair_eval(m, s, c, X, G, a)) return;
+    if (!pair_eval(ax, m, s, c, X, G, a)) return;
     float phi, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     phi_ge_t<FN>(H, a, c2, phi, g, e);
     vol_mom_add<mask_top(1 << FN)>(G, phi, g, e, X, M);
@@ -1003,9 +1053,9 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
                     rr = fmaxf(rr, __shfl_xor(rr, o));
                 }
                 ml[d] = mn; mh[d] = mx; R[d] = rr;
-                const float ghi = h.lo[d] + h.cs[d] * h.n[d];
-                const Win wa = image_range(mn, rr, h.lo[d], ghi, false);
-                const Win wb = image_range(mx, rr, h.lo[d], ghi, false);
+                const HdrAx &hx = hax_of(buf);  // (an open axis: the direct image only)
+                const Win wa = image_range(mn, rr, hx.ilo[d], hx.ihi[d], false);
+                const Win wb = image_range(mx, rr, hx.ilo[d], hx.ihi[d], false);
                 w[d].k0 = min(wa.k0, wb.k0);
                 w[d].k1 = max(wa.k1, wb.k1);
             }
@@ -1053,9 +1103,9 @@ __global__ __launch_bounds__(kWave) void k_vol_backward(const char *__restrict__
                                             }
                                             if (mine) {
                                                 if constexpr (CB == 1)
-                                                    bwd_pair_t<FN>(m, c, c2, sv, &shrow[u][0], mom);
+                                                    bwd_pair_t<FN>(Torus{}, m, c, c2, sv, &shrow[u][0], mom);
                                                 else
-                                                    bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sv,
+                                                    bwd_pair<FN, CB>(Torus{}, m, c, values, g, C, cbase, nch, sv,
                                                                      hs + (int64_t)__float_as_int(sp.w) * KU * C, dm,
                                                                      dc, dv, cf);
                                             }
@@ -1085,6 +1135,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward writes the NaN)
+    const Axes ax = axes_of(buf);
     const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
     const int nch = min(CB, C - cbase);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -1097,7 +1148,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big(const char *__restr
         for (int k = 0; k < NV; ++k) v[k] = 0.0f;
         for (int sid = threadIdx.x; sid < N; sid += kBlock) {
             const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
-            bwd_pair<FN, CB>(m, c, values, g, C, cbase, nch, sp,
+            bwd_pair<FN, CB>(ax, m, c, values, g, C, cbase, nch, sp,
                              hs + (int64_t)sid * VTr<FN>::KU * C, v, v + 3, v + 9, cf);
         }
         for (int k = 0; k < NV; ++k)
@@ -1197,10 +1248,10 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
             for (int d = 0; d < 3; ++d) s[d] = active ? samples[(int64_t)sid * 3 + d] : 0.0f;
             float acc[SKU];
             for (int u = 0; u < SKU; ++u) acc[u] = 0.0f;
-            auto eval = [&](const float *m, const float *c, float v, auto big) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, float v, auto big) {
                 constexpr bool BIG = decltype(big)::value;
                 float X[3], a[3], G;
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 if constexpr ((MASK & 1) != 0) fwd_acc<0, BIG>(v, G, a, c, acc + O0);
                 if constexpr ((MASK & 2) != 0) fwd_acc<1, BIG>(v, G, a, c, acc + O1);
                 if constexpr ((MASK & 4) != 0) fwd_acc<2, BIG>(v, G, a, c, acc + O2);
@@ -1209,15 +1260,16 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_m(const char *__restrict_
                 if constexpr ((MASK & 32) != 0) fwd_acc<kFnOp, BIG>(v, G, a, c, acc + O5, cf);
             };
             walk_candidates<1>(
-                h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
-                [&](const float *m, const float *c, const float *vr) { eval(m, c, vr[0], std::false_type{}); });
+                h, hax_of(buf), bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
+                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr[0], std::false_type{}); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
-                    eval(m, c, values[g], std::true_type{});
+                    eval(ax, m, c, values[g], std::true_type{});
                 }
                 if constexpr ((MASK & 1) != 0) fwd_store<0>(outs.p[0], sid, acc + O0);
                 if constexpr ((MASK & 2) != 0) fwd_store<1>(outs.p[1], sid, acc + O1);
@@ -1321,9 +1373,9 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                     rr = fmaxf(rr, __shfl_xor(rr, o));
                 }
                 ml[d] = mn; mh[d] = mx; R[d] = rr;
-                const float ghi = h.lo[d] + h.cs[d] * h.n[d];
-                const Win wa = image_range(mn, rr, h.lo[d], ghi, false);
-                const Win wb = image_range(mx, rr, h.lo[d], ghi, false);
+                const HdrAx &hx = hax_of(buf);  // (an open axis: the direct image only)
+                const Win wa = image_range(mn, rr, hx.ilo[d], hx.ihi[d], false);
+                const Win wb = image_range(mx, rr, hx.ilo[d], hx.ihi[d], false);
                 w[d].k0 = min(wa.k0, wb.k0);
                 w[d].k1 = max(wa.k1, wb.k1);
             }
@@ -1375,7 +1427,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_m(const char *__restrict
                                             }
                                             if (!mine) continue;
                                             float X[3], a[3], G;
-                                            if (!pair_eval(m, sv, c, X, G, a)) continue;
+                                            if (!pair_eval(Torus{}, m, sv, c, X, G, a)) continue;
                                             const float *H = &shrow[u][0];
                                             float phi = 0.0f, gg[3] = {0.0f, 0.0f, 0.0f};
                                             float ee[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -1414,6 +1466,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_m writes the NaN)
+    const Axes ax = axes_of(buf);
     const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     for (int b = blockIdx.x; b < h.nbig; b += gridDim.x) {
@@ -1428,17 +1481,17 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_m(const char *__res
             const float sp[3] = {samples[(int64_t)sid * 3], samples[(int64_t)sid * 3 + 1], samples[(int64_t)sid * 3 + 2]};
             const float *hrow = hs + (int64_t)sid * SKU;
             if constexpr ((MASK & 1) != 0)
-                bwd_pair<0, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 0), v, v + 3, v + 9);
+                bwd_pair<0, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 0), v, v + 3, v + 9);
             if constexpr ((MASK & 2) != 0)
-                bwd_pair<1, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 1), v, v + 3, v + 9);
+                bwd_pair<1, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 1), v, v + 3, v + 9);
             if constexpr ((MASK & 4) != 0)
-                bwd_pair<2, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
+                bwd_pair<2, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 2), v, v + 3, v + 9);
             if constexpr ((MASK & 8) != 0)
-                bwd_pair<3, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
+                bwd_pair<3, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, 3), v, v + 3, v + 9);
             if constexpr ((MASK & 16) != 0)
-                bwd_pair<kFnTrace, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnTrace), v, v + 3, v + 9);
+                bwd_pair<kFnTrace, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnTrace), v, v + 3, v + 9);
             if constexpr ((MASK & 32) != 0)
-                bwd_pair<kFnOp, 1>(m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnOp), v, v + 3, v + 9, cf);
+                bwd_pair<kFnOp, 1>(ax, m, c, values, g, 1, 0, 1, sp, hrow + mask_off(MASK, kFnOp), v, v + 3, v + 9, cf);
         }
         for (int k = 0; k < NV; ++k)
             for (int o = kWave / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
@@ -1527,9 +1580,9 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 if constexpr ((MASK & 32) != 0) sg_load_h<kFnOp>(dLs.p[S5], sid, H + O5);
             }
             float ds[3] = {0.0f, 0.0f, 0.0f};
-            auto eval = [&](const float *m, const float *c, float v) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, float v) {
                 float X[3], a[3], G;
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 const float c2[6] = {c[0], 2.0f * c[1], 2.0f * c[2], c[3], 2.0f * c[4], c[5]};
                 float phi = 0.0f, g[3] = {0.0f, 0.0f, 0.0f}, e[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // (e unused)
                 if constexpr ((MASK & 1) != 0) phi_ge_add<0>(H + O0, a, c2, phi, g, e);
@@ -1541,15 +1594,16 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_m(const char *__restrict__ 
                 sg_add(v * G, phi, a, c, g, ds);
             };
             walk_candidates<1>(
-                h, bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
-                [&](const float *m, const float *c, const float *vr) { eval(m, c, vr[0]); });
+                h, hax_of(buf), bin, conics, cand, lane, cc, active, s, [&](float *vr, int g) { vr[0] = values[g]; },
+                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr[0]); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
-                    eval(m, c, values[g]);
+                    eval(ax, m, c, values[g]);
                 }
                 for (int d = 0; d < 3; ++d) dsamples[(int64_t)sid * 3 + d] = ds[d];
             }
@@ -1603,9 +1657,9 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ bu
             auto values_of = [&](float *vr, int g) {
                 for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + cbase + ch] : 0.0f;
             };
-            auto eval = [&](const float *m, const float *c, const float *vr) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, const float *vr) {
                 float X[3], a[3], G;
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 float hv[KU];
                 for (int u = 0; u < KU; ++u) {
                     hv[u] = 0.0f;
@@ -1616,15 +1670,17 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad(const char *__restrict__ bu
                 phi_ge_t<FN>(hv, a, c2, phi, g, e, cf);
                 sg_add(G, phi, a, c, g, ds);
             };
-            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            walk_candidates<CB>(h, hax_of(buf), bin, conics, cand, lane, cc, active, s, values_of,
+                                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6], vr[CB];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
                     values_of(vr, g);
-                    eval(m, c, vr);
+                    eval(ax, m, c, vr);
                 }
                 for (int d = 0; d < 3; ++d) {
                     float *o = dsamples + (int64_t)sid * 3 + d;
@@ -1711,23 +1767,25 @@ __global__ __launch_bounds__(kWave) void k_vol_forward_mc(const char *__restrict
             auto values_of = [&](float *vr, int g) {
                 for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + ch] : 0.0f;
             };
-            auto eval = [&](const float *m, const float *c, const float *vr) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, const float *vr) {
                 float X[3], a[3], G;
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value;
                     fwd_acc_c<FN, CB>(nch, vr, G, a, c, acc + mask_off(MASK, FN), cf);
                 });
             };
-            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            walk_candidates<CB>(h, hax_of(buf), bin, conics, cand, lane, cc, active, s, values_of,
+                                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6], vr[CB];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
                     values_of(vr, g);
-                    eval(m, c, vr);
+                    eval(ax, m, c, vr);
                 }
                 for_mask<MASK>([&](auto fc) {
                     constexpr int FN = decltype(fc)::value, K = VTr<FN>::K, O = mask_off(MASK, FN);
@@ -1768,7 +1826,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_hsum_cat_c(int N, int C, const f
 // fills what the kernel keeps per staged sample, eval(slot, sv) takes a sample inside the lane's
 // own cut box.
 template <class Stage, class Eval>
-__device__ __forceinline__ void walk_samples(const Hdr &h, const int32_t *__restrict__ sids,
+__device__ __forceinline__ void walk_samples(const Hdr &h, const HdrAx &hx, const int32_t *__restrict__ sids,
                                              const int32_t *__restrict__ sstart, const float *__restrict__ samples,
                                              float4 *scand, int lane, bool active, const float *m, const float *r,
                                              Stage stage, Eval eval) {
@@ -1782,7 +1840,7 @@ __device__ __forceinline__ void walk_samples(const Hdr &h, const int32_t *__rest
             rr = fmaxf(rr, __shfl_xor(rr, o));
         }
         ml[d] = mn; mh[d] = mx; R[d] = rr;
-        w[d] = box_images(h, d, mn, mx, rr, false);
+        w[d] = box_images(hx, d, mn, mx, rr, false);
     }
     for (int kz = w[2].k0; kz <= w[2].k1; ++kz)
         for (int ky = w[1].k0; ky <= w[1].k1; ++ky)
@@ -1882,7 +1940,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restric
             };
             auto eval = [&](int slot, const float *sv) {
                 float X[3], a[3], G;
-                if (!pair_eval(m, sv, c, X, G, a)) return;
+                if (!pair_eval(Torus{}, m, sv, c, X, G, a)) return;
                 float hv[SKU];
                 for (int u = 0; u < SKU; ++u) hv[u] = 0.0f;
 #pragma unroll
@@ -1905,7 +1963,7 @@ __global__ __launch_bounds__(kWave) void k_vol_backward_mc(const char *__restric
                 });
                 vol_mom_add<TOP>(G, phi, gg, ee, X, mom);
             };
-            walk_samples(h, bin.sids, bin.sstart, samples, scand, lane, active, m, r, stage, eval);
+            walk_samples(h, hax_of(buf), bin.sids, bin.sstart, samples, scand, lane, active, m, r, stage, eval);
             float dm[3], dc[6], dphi[1];
             vol_mom_finish(c, mom, dm, dc, dphi);
             if (active) bwd_store<CB>(g, C, 0, nch, dm, dc, dv, dmeans, dvalues, dconics);
@@ -1930,6 +1988,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__re
     __shared__ float part[kWavesPerBlock][NV];
     const Hdr h = hdr_of(buf);
     if (vol_stale(buf, h, P, N)) return;  // (k_vol_backward_mc writes the NaN)
+    const Axes ax = axes_of(buf);
     const int32_t *__restrict__ gids = reinterpret_cast<const int32_t *>(buf + h.o_gids);
     const int nch = min(CB, C);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -1945,7 +2004,7 @@ __global__ __launch_bounds__(kBlock) void k_vol_backward_big_mc(const char *__re
             const float *hrow = hs + (int64_t)sid * SKU * C;
             for_mask<MASK>([&](auto fc) {
                 constexpr int FN = decltype(fc)::value;
-                bwd_pair<FN, CB>(m, c, values, g, C, 0, nch, sp, hrow + mask_off(MASK, FN) * C, v, v + 3, v + 9, cf);
+                bwd_pair<FN, CB>(ax, m, c, values, g, C, 0, nch, sp, hrow + mask_off(MASK, FN) * C, v, v + 3, v + 9, cf);
             });
         }
         for (int k = 0; k < NV; ++k)
@@ -2016,9 +2075,9 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__
             auto values_of = [&](float *vr, int g) {
                 for (int ch = 0; ch < CB; ++ch) vr[ch] = ch < nch ? values[(int64_t)g * C + ch] : 0.0f;
             };
-            auto eval = [&](const float *m, const float *c, const float *vr) {
+            auto eval = [&](const auto &ax, const float *m, const float *c, const float *vr) {
                 float X[3], a[3], G;
-                if (!pair_eval(m, s, c, X, G, a)) return;
+                if (!pair_eval(ax, m, s, c, X, G, a)) return;
                 float hv[SKU];
 #pragma unroll
                 for (int u = 0; u < SKU; ++u) {
@@ -2033,15 +2092,17 @@ __global__ __launch_bounds__(kWave) void k_vol_sgrad_mc(const char *__restrict__
                 });
                 sg_add(G, phi, a, c, g, ds);
             };
-            walk_candidates<CB>(h, bin, conics, cand, lane, cc, active, s, values_of, eval);
+            walk_candidates<CB>(h, hax_of(buf), bin, conics, cand, lane, cc, active, s, values_of,
+                                [&](const float *m, const float *c, const float *vr) { eval(Torus{}, m, c, vr); });
             if (active) {
+                const Axes ax = axes_of(buf);  // (the big Gaussians meet every sample: pair_eval needs the axes)
                 for (int q = bin.gstart[2 * h.ncells]; q < bin.gstart[2 * h.ncells + 1]; ++q) {  // big ones
                     const int g = bin.gids[q];
                     float m[3], c[6], vr[CB];
                     for (int d = 0; d < 3; ++d) m[d] = means[(int64_t)g * 3 + d];
                     for (int k = 0; k < 6; ++k) c[k] = conics[(int64_t)g * 6 + k];
                     values_of(vr, g);
-                    eval(m, c, vr);
+                    eval(ax, m, c, vr);
                 }
                 for (int d = 0; d < 3; ++d) dsamples[(int64_t)sid * 3 + d] = ds[d];
             }
@@ -2182,12 +2243,14 @@ static int fn_cb_case(int mask, int C) { return mask_top(mask) * 3 + (C <= 1 ? 0
 using namespace dgs;
 using namespace dgs::vol;
 
-extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const float *conics, const float *samples,
-                                     dgs_alloc_fn alloc, void *alloc_ctx, dgs_stream_t stream, int debug) {
+// Both binning entries; `who` names the caller's one in the error texts (dgs_volume_preprocess keeps its own).
+static int vol_preprocess(const char *who, int periodic, int P, int N, const float *means, const float *conics,
+                          const float *samples, dgs_alloc_fn alloc, void *alloc_ctx, dgs_stream_t stream, int debug) {
+    const auto err = [who](int code, const char *what) { return fail(code, std::string(who) + ": " + what); };
     if (P < 0 || N < 0 || !alloc || (P > 0 && (!means || !conics)) || (N > 0 && !samples))
-        return fail(DGS_ERR_ARG, "dgs_volume_preprocess: bad arguments");
+        return err(DGS_ERR_ARG, "bad arguments");
     if ((int64_t)P >= (1LL << 31) - 1 || (int64_t)N >= (1LL << 31) - 1)
-        return fail(DGS_ERR_ARG, "dgs_volume_preprocess: too many Gaussians or samples");
+        return err(DGS_ERR_ARG, "too many Gaussians or samples");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // cell cap: at most 128^3 cells, and no more than ~2 per point
     const int64_t cap = std::min<int64_t>((int64_t)kAxisCells * kAxisCells * kAxisCells,
@@ -2197,6 +2260,7 @@ extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const flo
     h.magic = kVolMagic;
     h.P = P;
     h.N = N;
+    h.open = ~periodic & 7;
     h.o_gext = kHdrBytes;
     h.o_gids = h.o_gext + a256((size_t)P * 16);
     h.o_sids = h.o_gids + a256((size_t)P * 4);
@@ -2210,13 +2274,13 @@ extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const flo
     h.o_flag = h.o_scopy + a256((size_t)N * 12);
     const size_t total = h.o_flag + 256;
     char *buf = static_cast<char *>(alloc(alloc_ctx, DGS_BUF_BINNING, total));
-    if (!buf) return fail(DGS_ERR_ALLOC, "dgs_volume_preprocess: binning buffer");
+    if (!buf) return err(DGS_ERR_ALLOC, "binning buffer");
     size_t sort_tmp = 0;
     DGS_TRY_HIP(onesweep_pairs<uint32_t>(nullptr, sort_tmp, nullptr, nullptr, nullptr, nullptr, (size_t)nmax, 0, 24, s));
     const size_t o_keys = 256, o_keys2 = o_keys + a256(nmax * 4), o_vals = o_keys2 + a256(nmax * 4),
                  o_tmp = o_vals + a256(nmax * 4);
     char *scr = static_cast<char *>(alloc(alloc_ctx, DGS_BUF_SCRATCH, o_tmp + a256(sort_tmp)));
-    if (!scr) return fail(DGS_ERR_ALLOC, "dgs_volume_preprocess: scratch");
+    if (!scr) return err(DGS_ERR_ALLOC, "scratch");
     Red *red = reinterpret_cast<Red *>(scr);
     uint32_t *keys = reinterpret_cast<uint32_t *>(scr + o_keys), *keys2 = reinterpret_cast<uint32_t *>(scr + o_keys2);
     uint32_t *vals = reinterpret_cast<uint32_t *>(scr + o_vals);
@@ -2234,7 +2298,7 @@ extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const flo
     for (int d = 0; d < 3; ++d) {
         float lo = std::min(hr.mlo[d], hr.slo[d]), hi = std::max(hr.mhi[d], hr.shi[d]);
         if (!(lo <= hi)) lo = hi = 0.0f;  // (no small Gaussian and no sample)
-        if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(DGS_ERR_ARG, "dgs_volume_preprocess: non-finite samples");
+        if (!std::isfinite(lo) || !std::isfinite(hi)) return err(DGS_ERR_ARG, "non-finite samples");
         h.lo[d] = lo;
         h.E[d] = hr.E[d];
         const float ext = hi - lo;
@@ -2292,9 +2356,30 @@ extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const flo
     if (P > 0) DGS_TRY_HIP(hipMemcpyAsync(buf + h.o_ccopy, conics, (size_t)P * 24, hipMemcpyDeviceToDevice, s));
     if (N > 0) DGS_TRY_HIP(hipMemcpyAsync(buf + h.o_scopy, samples, (size_t)N * 12, hipMemcpyDeviceToDevice, s));
     DGS_TRY_HIP(hipMemsetAsync(buf + h.o_flag, 0, 4, s));
-    k_vol_header<<<1, 64, 0, s>>>(h, buf);
+    HdrAx hx;
+    for (int d = 0; d < 3; ++d) {
+        const bool open = (h.open >> d) & 1;
+        hx.ilo[d] = open ? INFINITY : h.lo[d];
+        hx.ihi[d] = open ? -INFINITY : h.lo[d] + h.cs[d] * h.n[d];
+        hx.lim[d] = open ? INFINITY : 1.0f;
+    }
+    k_vol_header<<<1, 64, 0, s>>>(h, hx, buf);
     DGS_LAUNCH_CHECK(s, debug);
     return DGS_OK;
+}
+
+extern "C" int dgs_volume_preprocess_axes(int periodic, int P, int N, const float *means, const float *conics,
+                                          const float *samples, dgs_alloc_fn alloc, void *alloc_ctx,
+                                          dgs_stream_t stream, int debug) {
+    if (periodic < 0 || periodic > 7)
+        return fail(DGS_ERR_ARG, "dgs_volume_preprocess_axes: periodic must be 0..7 (bit d: axis d periodic)");
+    return vol_preprocess("dgs_volume_preprocess_axes", periodic, P, N, means, conics, samples, alloc, alloc_ctx, stream,
+                          debug);
+}
+
+extern "C" int dgs_volume_preprocess(int P, int N, const float *means, const float *conics, const float *samples,
+                                     dgs_alloc_fn alloc, void *alloc_ctx, dgs_stream_t stream, int debug) {
+    return vol_preprocess("dgs_volume_preprocess", 7, P, N, means, conics, samples, alloc, alloc_ctx, stream, debug);
 }
 
 // ---- the calls (include/dgs_volume.h).  A function is the single-bit mask 1 << function; a

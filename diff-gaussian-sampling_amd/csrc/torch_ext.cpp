@@ -1017,17 +1017,25 @@ void vol_shapes(const Tensor &means, const Tensor &conics, const Tensor &samples
     TORCH_CHECK(samples.dim() == 2 && samples.size(1) == 3, "volume: samples must be [N, 3]");
 }
 
-Tensor VolumePreprocess(const Tensor &means_in, const Tensor &conics_in, const Tensor &samples_in,
-                        const bool debug) {
+// periodic_mask: bit d set = axis d periodic (dgs_volume_preprocess_axes; 7 is volume_preprocess)
+Tensor VolumePreprocessAxes(const Tensor &means_in, const Tensor &conics_in, const Tensor &samples_in,
+                            int64_t periodic_mask, const bool debug) {
     const Tensor means = f32(means_in, "means"), conics = f32(conics_in, "conics");
     const Tensor samples = f32(samples_in, "samples");
     vol_shapes(means, conics, samples);
+    if (periodic_mask < 0 || periodic_mask > 7)  // (ValueError, as preprocess_volume raises)
+        throw pybind11::value_error("volume: periodic_mask must be 0..7 (bit d set: axis d periodic)");
     AllocCtx ctx{means.device(), {}, {}};
-    check(dgs_volume_preprocess((int)means.size(0), (int)samples.size(0), means.data_ptr<float>(),
-                                conics.data_ptr<float>(), samples.data_ptr<float>(), alloc_cb, &ctx,
-                                as_dgs(cur_stream()), debug ? 1 : 0),
+    check(dgs_volume_preprocess_axes((int)periodic_mask, (int)means.size(0), (int)samples.size(0),
+                                     means.data_ptr<float>(), conics.data_ptr<float>(), samples.data_ptr<float>(),
+                                     alloc_cb, &ctx, as_dgs(cur_stream()), debug ? 1 : 0),
           "volume_preprocess");
     return ctx.bufs[DGS_BUF_BINNING];
+}
+
+Tensor VolumePreprocess(const Tensor &means_in, const Tensor &conics_in, const Tensor &samples_in,
+                        const bool debug) {
+    return VolumePreprocessAxes(means_in, conics_in, samples_in, 7, debug);
 }
 
 Tensor VolumeForward(int function, const Tensor &means_in, const Tensor &values_in, const Tensor &conics_in,
@@ -1594,6 +1602,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         return std::make_tuple(c[0], c[1], c[2], c[3]);
     });
     m.def("volume_preprocess", &VolumePreprocess);
+    m.def("volume_preprocess_axes", &VolumePreprocessAxes);
     m.def("volume_forward", &VolumeForward);
     m.def("volume_backward", &VolumeBackward);
     m.def("volume_forward_multi", &VolumeForwardMulti);

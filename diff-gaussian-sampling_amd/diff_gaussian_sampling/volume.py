@@ -24,6 +24,12 @@ requires_grad: without the flag, samples that require a gradient raise NotImplem
 before.  With it, `samples.grad` is filled (the pair set held fixed, the wrap with slope 1, as
 for the other gradients), and the gradients of means, values and conics are bit for bit what they
 are without it.
+
+The wrap is a choice per axis (`periodic=` of `preprocess_volume` and `VolumeSampler`; DESIGN.md
+§4.8, "Open axes"): by default every axis is periodic with period 2; on an open axis X_d is the
+plain difference mean_d - sample_d and only the direct image exists, which is what a time axis or an
+axis with walls needs.  The choice is fixed at binning time and stored in the binning, so
+`sample_volume` and `sample_volume_multi` follow it with no argument of their own.
 """
 import torch
 
@@ -140,9 +146,24 @@ def _multi_calls(codes, coef=None):
     return _C.volume_forward_multi, _C.volume_backward_multi, _C.volume_samples_backward
 
 
-def preprocess_volume(means, conics, samples, debug=False):
-    """Cell binning of a D = 3 field; returns the opaque uint8 buffer."""
-    return call_debug(_C.volume_preprocess, debug, "vol_preprocess", means, conics, samples, debug)
+def _axes(periodic):
+    """`periodic` as a tuple of three bools (axis 0, 1, 2): a bool for all three, or three bools."""
+    if isinstance(periodic, bool):
+        return (periodic,) * 3
+    if isinstance(periodic, (tuple, list)) and len(periodic) == 3 and all(isinstance(p, bool) for p in periodic):
+        return tuple(periodic)
+    raise ValueError(f"periodic is a bool or three bools for (axis 0, axis 1, axis 2), not {periodic!r}")
+
+
+def preprocess_volume(means, conics, samples, debug=False, periodic=True):
+    """Cell binning of a D = 3 field; returns the opaque uint8 buffer.  `periodic`: a bool, or three
+    bools for (axis 0, 1, 2); False makes an axis open (no wrap, only the direct image: a time axis,
+    an axis with walls).  The binning carries the axes: every call on it follows them."""
+    axes = _axes(periodic)
+    if all(axes):  # the default: the call it has always been
+        return call_debug(_C.volume_preprocess, debug, "vol_preprocess", means, conics, samples, debug)
+    mask = sum(1 << d for d in range(3) if axes[d])
+    return call_debug(_C.volume_preprocess_axes, debug, "vol_preprocess", means, conics, samples, mask, debug)
 
 
 class _SampleVolume(torch.autograd.Function):
@@ -297,14 +318,21 @@ class VolumeSampler:
     one more walk of the candidates per backward, about a forward's time, which is why it is asked
     for and not inferred from requires_grad; the default raises NotImplementedError for such
     samples.  Samples stepped in place (`samples -= lr * samples.grad` under no_grad) are re-binned
-    by the next call like any other changed tensor."""
+    by the next call like any other changed tensor.
 
-    def __init__(self, debug=False, sample_grad=False):
+    periodic=True wraps every axis with period 2 (the torus of the reference's D = 2 rule).  A bool per
+    axis, `periodic=(True, True, False)`, makes an axis open: no wrap and no images, coordinates of
+    any finite value, so that a Gaussian near t = +1 of an (x, y, t) field does not reach the samples
+    near t = -1 ("Open axes").  The axes are kept (`.periodic`, three bools), used by
+    `preprocess` and by every automatic re-bin, and carried by the binning to every call."""
+
+    def __init__(self, debug=False, sample_grad=False, periodic=True):
         self.debug = debug
         self.sample_grad = sample_grad
+        self.periodic = _axes(periodic)
 
     def preprocess(self, means, values, covariances, conics, samples):
-        self.binning = preprocess_volume(means, conics, samples, self.debug)
+        self.binning = preprocess_volume(means, conics, samples, self.debug, self.periodic)
         self.means, self.values, self.conics, self.samples = means, values, conics, samples
         self._versions = self._now()
         self._fresh = True
@@ -320,7 +348,7 @@ class VolumeSampler:
         # changed in place since the binning (or, for inference tensors, possibly changed: every
         # call after the first re-bins) -> re-bin
         if (now is None and not self._fresh) or now != self._versions:
-            self.binning = preprocess_volume(self.means, self.conics, self.samples, self.debug)
+            self.binning = preprocess_volume(self.means, self.conics, self.samples, self.debug, self.periodic)
             self._versions = self._now()
         self._fresh = False
 

@@ -5,7 +5,8 @@
  * backward.cu:108-416), its radius is 0 there (forward.cu:52-61) and its sample keys are left
  * uninitialised (sampler_impl.cu:177-182), so at D = 3 it renders nothing.  This path is the
  * reference's per-pair arithmetic carried to three dimensions:
- *   X_d   = mean_d - sample_d, wrapped as forward.cu:149-157 does per axis (period 2)
+ *   X_d   = mean_d - sample_d, wrapped as forward.cu:149-157 does per axis (period 2; an axis
+ *           may be open instead, dgs_volume_preprocess_axes below)
  *   power = -0.5f * (c00 X0 X0 + c11 X1 X1 + c22 X2 X2) - (c01 X0 X1 + c02 X0 X2 + c12 X1 X2),
  *           conics packed [c00 c01 c02 c11 c12 c22] (the reference's D(D+1)/2 row-major
  *           upper triangle, sample_points.cu:40); a pair with power > 0 is skipped
@@ -42,6 +43,30 @@ extern "C" {
 int dgs_volume_preprocess(int P, int N, const float *means, const float *conics,
                           const float *samples, dgs_alloc_fn alloc, void *alloc_ctx,
                           dgs_stream_t stream, int debug);
+
+/* Open (non-periodic) axes ("Open axes"): the binning with a choice of the wrap per
+ * axis, for a time axis or an axis with walls, where a Gaussian near +1 must not reach the samples
+ * near -1.  `periodic` is a mask in 0..7, bit d set = axis d periodic; any other value returns
+ * DGS_ERR_ARG before any device work.  dgs_volume_preprocess is the periodic = 7 call of this one.
+ * On a periodic axis nothing changes.  On an open axis d
+ *   X_d = fl(mean_d - sample_d), not wrapped;
+ *   only the direct image exists: a pair contributes through its raw distance or not at all;
+ *   the coordinates need not lie in [-1, 1]: any finite values are accepted.  In practice keep
+ *   |coordinate| below about 100: the cell windows and the cut box test carry an absolute slack of
+ *   1e-5, which one fp32 ulp of a coordinate exceeds from about 128 on; beyond that a candidate
+ *   exactly on the edge of its cut box (where G is 0 or a subnormal) can be left out, and from
+ *   about 1e4 on fp32 no longer resolves the displacements themselves.
+ * Everything after X is as above: the power in its stated order without contraction, the
+ * power > 0 skip, the exact-zero skip, a = A X, the terms of every function, the classification
+ * of the Gaussians and their cut half-widths.  The gradients use the same X (nothing is wrapped
+ * on an open axis, so the "wrap with slope 1" does not arise there).
+ * The axes are fixed at binning time and stored in the binning buffer: every forward, backward,
+ * sample-gradient and count_pairs entry below follows them with an unchanged argument list, and
+ * the stale buffer / changed input guard is the same.  A new exported function only:
+ * DGS_ABI_VERSION is unchanged. */
+int dgs_volume_preprocess_axes(int periodic, int P, int N, const float *means, const float *conics,
+                               const float *samples, dgs_alloc_fn alloc, void *alloc_ctx,
+                               dgs_stream_t stream, int debug);
 
 /* Workspace bytes of dgs_volume_backward (0 for the forward). */
 size_t dgs_volume_workspace_size(int function, int P, int N, int C, int backward);

@@ -475,3 +475,40 @@ def volume_samples_backward_linop(codes, coef, means, values, conics, samples, d
         mask, cf, P, N, C, _ptr(means), _ptr(values), _ptr(conics), _ptr(samples), ptrs, _ptr(binning),
         binning.numel(), _ptr(ds), None, 0, _stream(), int(bool(debug))))
     return ds
+
+
+# ---- D = 3 fields: the binning with a choice of the wrap per axis (dgs_volume_preprocess_axes:
+# `periodic` is a mask in 0..7, bit d set = axis d periodic; 7 is dgs_volume_preprocess) and the
+# diagnostic pair counts, which follow the binning's axes like every other entry.
+_lib.dgs_volume_preprocess_axes.argtypes = [_I] * 3 + [_P] * 3 + [ALLOC_FN, _P, _P, _I]
+_lib.dgs_volume_preprocess.argtypes = [_I] * 2 + [_P] * 3 + [ALLOC_FN, _P, _P, _I]
+_lib.dgs_volume_count_pairs.argtypes = [_I] * 2 + [_P] * 3 + [_P, _SZ, ctypes.POINTER(_I64), _P]
+
+
+def volume_preprocess_axes(means, conics, samples, periodic, debug):
+    """The binning buffer (a uint8 tensor) of a D = 3 field; periodic=None calls dgs_volume_preprocess."""
+    means, conics, samples = map(_f32, (means, conics, samples))
+    P, N = means.shape[0], samples.shape[0]
+    buffers = {}
+
+    def alloc(ctx, which, nbytes):  # DGS_BUF_* -> device memory owned by torch
+        t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=means.device)
+        buffers.setdefault(which, []).append(t)
+        return t.data_ptr()
+
+    tail = (P, N, _ptr(means), _ptr(conics), _ptr(samples), ALLOC_FN(alloc), None, _stream(), int(bool(debug)))
+    if periodic is None:
+        _check(_lib.dgs_volume_preprocess(*tail))
+    else:
+        _check(_lib.dgs_volume_preprocess_axes(int(periodic), *tail))
+    torch.cuda.current_stream().synchronize()  # (the scratch buffer goes back to torch's allocator here)
+    return buffers[0][-1]
+
+
+def volume_count_pairs(means, conics, samples, binning):
+    """(pairs the forward evaluates, live pairs with G > 0) through dgs_volume_count_pairs."""
+    means, conics, samples = map(_f32, (means, conics, samples))
+    counts = (_I64 * 2)()
+    _check(_lib.dgs_volume_count_pairs(means.shape[0], samples.shape[0], _ptr(means), _ptr(conics), _ptr(samples),
+                                       _ptr(binning), binning.numel(), counts, _stream()))
+    return counts[0], counts[1]

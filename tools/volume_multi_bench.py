@@ -2,7 +2,7 @@
 
     python tools/volume_multi_bench.py [--P 1000000] [--grid3 64] [--functions gaussian,laplacian,...]
                                        [--rounds 3] [--steps 3] [--C 3] [--separate-only] [--trace-vs-hessian]
-                                       [--operator-vs-multi]
+                                       [--operator-vs-multi] [--periodic 110]
 
 The workload is `bench.py --op volume`'s (syn.gaussians3, a g^3 lattice; C = 1 unless --C).  After settle
 steps, fused and separate steps alternate for `--rounds` rounds in one process, so clock drift
@@ -10,6 +10,7 @@ hits both alike; each figure is the median over the rounds of the mean ms per fo
 backward step (preprocess excluded).  Prints one JSON line: fused_ms, separate_ms (the sum of the
 per-function calls, same outputs and gradients), per-function step times `single_ms`, the speedup,
 and `fused_over_last`, the fused step against the most expensive (last named) function alone.
+--periodic 110 bins the field with axis 2 open (one 0/1 per axis; DESIGN.md 4.8, "Open axes").
 --separate-only times the per-function calls only (a package without the fused call, for A/B
 runs through tools/ab.py --script); --C sets the channel count (the fused call shares one walk up
 to C = 4; with more channels, or in a package from before that, it is the per-function calls added:
@@ -60,6 +61,9 @@ def main():
     ap.add_argument("--trace-vs-hessian", action="store_true")
     ap.add_argument("--operator-vs-multi", action="store_true")
     ap.add_argument("--C", type=int, default=1, help="channels")
+    ap.add_argument("--periodic", default=os.environ.get("DGS_VOLUME_BENCH_PERIODIC", "111"),
+                    help="one 0/1 per axis, 0: the axis is open (VolumeSampler(periodic=...)); the default also "
+                         "from DGS_VOLUME_BENCH_PERIODIC, which tools/ab.py's base:K=V form can set per variant")
     args = ap.parse_args()
     C = args.C
     fns = args.functions.split(",")
@@ -69,7 +73,10 @@ def main():
     N = samples.shape[0]
     for t in (means, values, conics):
         t.requires_grad_(True)
-    vs = VolumeSampler(False)
+    axes = tuple(ch == "1" for ch in args.periodic)
+    assert len(axes) == 3 and set(args.periodic) <= {"0", "1"}, "--periodic is three of 0/1"
+    # (all periodic: the call every package has, so a build of a parent commit runs it too)
+    vs = VolumeSampler(False) if all(axes) else VolumeSampler(False, periodic=axes)
     vs.preprocess(means, values, covs, conics, samples)
     gen = torch.Generator().manual_seed(5)
     if args.operator_vs_multi:
@@ -111,7 +118,7 @@ def main():
             times[k].append(timed(k))
     med = {k: statistics.median(v) for k, v in times.items()}
     res = {"P": args.P, "N": N, "C": C, "grid3": args.grid3, "functions": fns, "rounds": args.rounds, "steps": args.steps,
-           "separate_ms": med["separate"], "single_ms": {f: med[f] for f in fns},
+           "periodic": args.periodic, "separate_ms": med["separate"], "single_ms": {f: med[f] for f in fns},
            "separate_rounds_ms": times["separate"]}
     if not args.separate_only:
         res.update(fused_ms=med["fused"], fused_rounds_ms=times["fused"], speedup=med["separate"] / med["fused"],
